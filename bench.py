@@ -9,14 +9,29 @@ gathered to rank 0 over RCCL, then put back in row order.  Inputs (the compiled 
 are resident in HBM before the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scene s64] [--size 4096] [--depth 5]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline needs and no more: it prepares the scene, renders one untimed
+frame on a context of its own (see main()), settles the clocks, runs the W warmup and the K timed
+steps, writes the last timed step's frame if --dump-outputs is given, and prints the result line
+(metric, value, ms_per_step, config, kernel_ms).  --full adds every other leg, each outside the
+timed region: the work count from that first frame's levels, the multi-GPU self-check, the dominant
+kernel timed alone and the rooflines, the setup costs, the C-ABI boundary legs and the CPU baseline.
+
+--dump-outputs DIR writes what a caller of the timed path receives from its last step (the frame:
+FrameRenderer's slab at N = 1, rank 0's gathered frame at N > 1) as DIR/frame.npy, float32 or
+float64 as the framebuffer, shape (rows, W, 3).  A frame over 48 MiB is sampled by rows: a fixed,
+seeded choice of rows in ascending order, their indices in DIR/frame_rows.npy (float64).  The scene,
+camera and jitter seed are fixed by the arguments, so two runs with the same arguments write the
+same file.
 
 With --gpus N > 1 outside torch.distributed.run (no WORLD_SIZE in the environment), bench.py
 starts ``python -m torch.distributed.run --nnodes 1 --nproc-per-node N --master-addr 127.0.0.1
 --master-port <free> bench.py <same arguments>`` as a child process, before anything touches
 the GPU, and exits with its return code (it does not exec).
 
-Rank 0 prints ONE JSON line.  Extra keys: "roofline" (the binding FP64-VALU roofline of
+Rank 0 prints ONE JSON line.  Extra keys with --full: "roofline" (the binding FP64-VALU roofline of
 the render kernel), "roofline_hbm" (the memory roofline the north star asks for),
 "cpu_baseline" (the C oracle running the reference's literal recursion on the host's
 cores over a bounded sample of the same frame — the BEAM is not installed on the box),
@@ -63,13 +78,20 @@ def parse():
     ap.add_argument("--row-block", type=int, default=16)
     ap.add_argument("--spp", type=int, default=1, help="samples per pixel (RT_SUPERSAMPLING; BASELINE config 5: 16)")
     ap.add_argument("--seed", type=int, default=0x5EED0005)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's frame to DIR/frame.npy (a seeded "
+                         "sample of rows, listed in DIR/frame_rows.npy, when the frame is over 48 MiB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs outside the headline: work count (levels), multi-GPU self-check, the dominant "
+                         "kernel alone and the rooflines, setup costs, boundary legs, CPU baseline (each can be "
+                         "switched off: --iso 0, --no-setup, --no-boundary, --no-cpu-baseline)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample time")
     ap.add_argument("--settle", type=float, default=0.3,
                     help="seconds of untimed frames before the warmup steps (clock ramp; 0 = none)")
     ap.add_argument("--iso", type=int, default=20,
-                    help="frames launched back to back after the timed region to time the dominant kernel alone")
+                    help="--full: frames launched back to back after the timed region to time the dominant kernel alone")
     ap.add_argument("--span-timing", action="store_true",
-                    help="also bracket the dominant kernel with HIP events inside the timed region "
+                    help="--full: also bracket the dominant kernel with HIP events inside the timed region "
                          "(launch_span_ms_in_flight; off by default: the timed frames run as the product runs them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-boundary", action="store_true")
@@ -270,23 +292,33 @@ def main():
                        priorities=("auto" if args.priorities == "auto" else None if args.priorities == "none" else
                                    parse_priorities(args.priorities)), assemble=assemble)
 
-    # untimed: work count of this rank's rows (levels of every pixel's reflection chain)
-    lv_fr = FrameRenderer(scene, W, H, args.depth, rank=rank, world=world, device=local, row_block=args.row_block,
-                          precision=args.precision, order=args.order, levels=True, assemble=assemble)
     from eraytracer_amd.dist import shard_global_rows
+    # untimed: one frame on a context of its own (one frame in flight, so with the library's two
+    # shading side streams) before the slot streams render their first.  The hardware queues the
+    # process opens for it decide how the slot streams share queues afterwards, and the headline
+    # has always been measured after it: S64 4096^2 depth 5, 20 steps after 5, three runs each,
+    # 0.374-0.381 ms per frame with this frame, 0.386-0.391 with its side streams off, 0.389-0.401
+    # without it.  --full renders it with levels: the work count of this rank's rows (levels of
+    # every pixel's reflection chain).
+    lv_fr = FrameRenderer(scene, W, H, args.depth, rank=rank, world=world, device=local, row_block=args.row_block,
+                          precision=args.precision, order=args.order, levels=args.full, assemble=assemble)
+    ops_rank = px_rank = None
     if lv_fr.renders:
         lv_fr.launch()
         torch.cuda.synchronize()
-        valid = torch.from_numpy(shard_global_rows(H, args.row_block, lv_fr.nshards, lv_fr.shard) >= 0)
-        valid = valid.to(lv_fr.levels.device)
-        hist = torch.bincount(lv_fr.levels[valid].flatten().to(torch.int64), minlength=args.depth + 1).cpu().numpy()
-    else:  # an assembling rank 0 renders no pixels
-        hist = np.zeros(args.depth + 1, dtype=np.int64)
+    if args.full:
+        if lv_fr.renders:
+            valid = torch.from_numpy(shard_global_rows(H, args.row_block, lv_fr.nshards, lv_fr.shard) >= 0)
+            valid = valid.to(lv_fr.levels.device)
+            hist = torch.bincount(lv_fr.levels[valid].flatten().to(torch.int64),
+                                  minlength=args.depth + 1).cpu().numpy()
+        else:  # an assembling rank 0 renders no pixels
+            hist = np.zeros(args.depth + 1, dtype=np.int64)
+        # with spp > 1 the work is estimated as spp times that of the unjittered frame
+        ops_rank = workload.ops_from_levels(hist, args.depth, counts) * args.spp
+        px_rank = int(hist.sum())
     lv_fr.close()
     del lv_fr
-    # with spp > 1 the work is estimated as spp times that of the unjittered frame
-    ops_rank = workload.ops_from_levels(hist, args.depth, counts) * args.spp
-    px_rank = int(hist.sum())
 
     # With N > 1 ranks a step is render + gather to rank 0 + reorder; frames are pipelined
     # (frame i+1 renders while frame i's gather is in flight, dist.SlabPipeline) and the
@@ -297,7 +329,7 @@ def main():
     checked = None
     if world > 1:
         pipe = fr.compact_gather() if args.gather == "compact" else fr.pipeline()
-        if args.gather == "compact":
+        if args.gather == "compact" and args.full:
             checked = self_check(fr, pipe, scene, args, rank, world, local)
 
     def one_step():
@@ -333,7 +365,8 @@ def main():
     # the dominant kernel's launches are bracketed by events on their own streams
     engine = engine_of(N, fr, args.spp)
     dom_label, dom_kt, dom_desc = DOMINANT[engine]
-    if args.span_timing:
+    span_timing = args.span_timing and args.full
+    if span_timing:
         fr.time_kernels(getattr(N, dom_kt))
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     if world > 1:
@@ -355,29 +388,64 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     kern_ms = e0.elapsed_time(e1) / args.steps
-    span_ms, span_n = fr.kernel_time(getattr(N, dom_kt)) if args.span_timing else (None, 0)
-    fr.time_kernels(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fr, pipe, W, H)
+    span_ms, span_n = fr.kernel_time(getattr(N, dom_kt)) if span_timing else (None, 0)
+    if span_timing:
+        fr.time_kernels(0)
     # The dominant kernel alone: with frames in flight a launch's events also span the time it
     # queues behind other frames' kernels, so its duration is timed again over args.iso frames
     # launched back to back on one context and stream (consecutive launches serialise; rocprof's
     # trace of the same run shows these as the last frames: scripts/pmc_summary.py "isolated")
-    dom_ms, dom_n = isolated_kernel_time(fr, getattr(N, dom_kt), args.iso) if args.iso > 0 else (None, 0)
+    dom_ms, dom_n = isolated_kernel_time(fr, getattr(N, dom_kt), args.iso) if args.full and args.iso > 0 \
+        else (None, 0)
 
     if world > 1:
         t = torch.tensor([elapsed, kern_ms], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kern_ms_max = float(t[0]), float(t[1])
-        o = torch.tensor([float(ops_rank)], dtype=torch.float64, device="cuda")
-        dist.all_reduce(o, op=dist.ReduceOp.SUM)
-        ops_total = float(o[0])
+        if args.full:
+            o = torch.tensor([float(ops_rank)], dtype=torch.float64, device="cuda")
+            dist.all_reduce(o, op=dist.ReduceOp.SUM)
+            ops_total = float(o[0])
     else:
         kern_ms_max = kern_ms
-        ops_total = float(ops_rank)
+        ops_total = float(ops_rank) if args.full else None
 
     if rank == 0:
         frame_px = W * H
         ms_step = elapsed / args.steps * 1e3
         value = frame_px * args.steps / elapsed / 1e6
+        line = {
+            "metric": "Mpixels/sec at 4096x4096, recursion depth 5 (frame rendered into HBM, gathered to rank 0)",
+            "value": round(value, 3),
+            "unit": "Mpixels/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "settle_frames": settle_frames,
+            "ms_per_step": round(ms_step, 4),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": f"{args.scene.upper()} {W}x{H} depth {args.depth}"
+                       + (f" x{args.spp} spp" if args.spp > 1 else ""), "scene": args.scene, "spp": args.spp,
+                       "width": W, "height": H, "depth": args.depth, "order": args.order,
+                       "framebuffer": args.precision, "row_block": args.row_block, "inflight": inflight,
+                       "engine": engine,
+                       "stream_priorities": [st.priority for st in fr.streams] if fr.streams else None,
+                       "parallelism": f"rows{world - 1 if assemble else world}" + (f"+rccl_{args.gather}_gather" if world > 1 else "")
+                       + ("+rank0_assembles" if assemble else ""),
+                       "world_size": world, "rccl_ranks": dist.get_world_size() if world > 1 else 1,
+                       "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4),
+                       "spheres": counts["spheres"], "triangles": counts["triangles"], "planes": counts["planes"],
+                       "lights": counts["lights"]},
+            "kernel_ms": round(kern_ms, 4),
+            "kernel_ms_max_rank": round(kern_ms_max, 4),
+        }
+    if rank == 0 and args.full:  # the legs outside the headline
         bytes_px = 12 if args.precision == "f32" else 24
         k_s = kern_ms / 1e3
         hbm_ach = px_rank * bytes_px / k_s / 1e9
@@ -447,32 +515,7 @@ def main():
                         "all of a frame's kernels over the GPU time per frame. ref_work_tops: the reference's "
                         "brute-force binary64 op count per frame (SURVEY.md 8d) / GPU time per frame, in T op/s "
                         "(culling skips most of it: not a roofline)")
-        line = {
-            "metric": "Mpixels/sec at 4096x4096, recursion depth 5 (frame rendered into HBM, gathered to rank 0)",
-            "value": round(value, 3),
-            "unit": "Mpixels/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "settle_frames": settle_frames,
-            "ms_per_step": round(ms_step, 4),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": f"{args.scene.upper()} {W}x{H} depth {args.depth}"
-                       + (f" x{args.spp} spp" if args.spp > 1 else ""), "scene": args.scene, "spp": args.spp,
-                       "width": W, "height": H, "depth": args.depth, "order": args.order,
-                       "framebuffer": args.precision, "row_block": args.row_block, "inflight": inflight,
-                       "engine": engine,
-                       "stream_priorities": [st.priority for st in fr.streams] if fr.streams else None,
-                       "parallelism": f"rows{world - 1 if assemble else world}" + (f"+rccl_{args.gather}_gather" if world > 1 else "")
-                       + ("+rank0_assembles" if assemble else ""),
-                       "world_size": world, "rccl_ranks": dist.get_world_size() if world > 1 else 1,
-                       "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4),
-                       "spheres": counts["spheres"], "triangles": counts["triangles"], "planes": counts["planes"],
-                       "lights": counts["lights"]},
+        line.update({
             "roofline": roof,
             "roofline_hbm": {"bound": "hbm", "achieved": round(hbm_ach, 3), "peak": PEAK_HBM_GBS, "unit": "GB/s",
                              "frac": round(hbm_ach / PEAK_HBM_GBS, 6), "traffic": traffic_frame,
@@ -481,11 +524,9 @@ def main():
                                      "frame; traffic = measured HBM bytes per frame launch (PMC; reads as FETCH_SIZE x2, the "
                                      "upper bound), traffic_low = the same with FETCH_SIZE x1 (lower bound; "
                                      "profiles/r04_hbm_calib.txt)"},
-            "kernel_ms": round(kern_ms, 4),
-            "kernel_ms_max_rank": round(kern_ms_max, 4),
             "kernel_mpx_s": round(px_rank / k_s / 1e6, 3),
             "ops_per_frame": ops_total,
-        }
+        })
         if checked is not None:
             line["self_check"] = checked
         if world == 1 and not args.no_setup:
@@ -494,11 +535,40 @@ def main():
             line.update(boundary_legs(N, scene, W, H, args))
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(scene, W, H, args.depth, args.cpu_seconds, args.spp, args.seed)
+    if rank == 0:
         print(json.dumps(line), flush=True)
     fr.close()
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 48 << 20   # --dump-outputs: frame.npy stays under this (the frame of the default workload is 192 MiB)
+DUMP_ROWS_SEED = 0x0D0B
+
+
+def dump_rows(H, row_bytes):
+    """The rows of an H-row frame that --dump-outputs writes: all of them when they fit in
+    DUMP_MAX_BYTES, else a fixed choice (numpy's PCG64 seeded with DUMP_ROWS_SEED) in ascending order."""
+    import numpy as np
+    k = max(1, DUMP_MAX_BYTES // row_bytes)
+    if k >= H:
+        return np.arange(H)
+    return np.sort(np.random.Generator(np.random.PCG64(DUMP_ROWS_SEED)).choice(H, size=k, replace=False))
+
+
+def dump_outputs(path, fr, pipe, W, H):
+    """--dump-outputs (rank 0, after the timed region has completed): the frame the last timed step
+    returned to its caller, the slab of fr.gather() at one rank (its rows are the frame's), the
+    gathered and reordered frame with more."""
+    import numpy as np
+    import torch
+    frame = fr.slab[:H] if pipe is None else fr.frame
+    rows = dump_rows(H, W * 3 * frame.element_size())
+    out = frame[torch.from_numpy(rows).to(frame.device)].cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frame.npy"), out)
+    np.save(os.path.join(path, "frame_rows.npy"), rows.astype(np.float64))
 
 
 def isolated_kernel_time(fr, kernel, frames):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of bench.py argument sets on one library: bash scripts/ab_args.sh TAG REPS "name1:args1" "name2:args2" ...
-# (each line: config name, Mpx/s, ms per frame, the dominant kernel's live launch time)
+# (each line: config name, Mpx/s, ms per frame, and with --full among the arguments the dominant kernel's live launch time)
 set -o pipefail
 TAG=$1; REPS=$2; shift 2
 mkdir -p gpurun_out

@@ -19,10 +19,10 @@ C5="--scene s256 --depth 8 --spp 16"
 b() { name=$1; shift; timeout -k 10 300 python bench.py "$@" > gpurun_out/${TAG}_bench_$name.json 2> gpurun_out/${TAG}_bench_$name.err || { tail -5 gpurun_out/${TAG}_bench_$name.err; exit 1; }; python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; print(sys.argv[2], d['value'], 'Mpx/s', d['ms_per_step'], 'ms/frame', 'dom', r.get('launch_ms_live'), 'frac', r.get('frac'), 'cpu', d.get('cpu_baseline', {}).get('value'), d.get('cpu_baseline', {}).get('cores'))" gpurun_out/${TAG}_bench_$name.json $name; }
 cfg_args() {
   case $1 in
-    c2q) echo "$C2 --no-cpu-baseline --no-boundary --no-setup" ;;
-    c3q) echo "--no-cpu-baseline --no-boundary --no-setup" ;;
-    c3dq) echo "--steps 20 --warmup 5 --no-cpu-baseline --no-boundary --no-setup" ;;
-    c5q) echo "$C5 --steps 8 --warmup 3 --no-boundary --no-cpu-baseline --no-setup" ;;
+    c2q) echo "$C2 --no-cpu-baseline --no-boundary --no-setup --full" ;;
+    c3q) echo "--no-cpu-baseline --no-boundary --no-setup --full" ;;
+    c3dq) echo "--steps 20 --warmup 5 --no-cpu-baseline --no-boundary --no-setup --full" ;;
+    c5q) echo "$C5 --steps 8 --warmup 3 --no-boundary --no-cpu-baseline --no-setup --full" ;;
   esac
 }
 case $PART in
@@ -65,22 +65,22 @@ test)
   bash scripts/debug_lists.sh run > gpurun_out/debug_lists_$TAG.log 2>&1 || { tail -30 gpurun_out/debug_lists_$TAG.log; exit 1; }
   tail -1 gpurun_out/debug_lists_$TAG.log ;;
 c3)
-  b c3d --steps 20 --warmup 5 --no-boundary --no-cpu-baseline || exit 1 ;;
+  b c3d --steps 20 --warmup 5 --no-boundary --no-cpu-baseline --full || exit 1 ;;
 setup)
-  b c3d --steps 20 --warmup 5 --no-boundary --no-cpu-baseline || exit 1
-  b c3d_q8 --steps 20 --warmup 5 --no-boundary --no-cpu-baseline --hw-queues 8 --no-setup || exit 1
-  b c5s $C5 --steps 6 --warmup 3 --no-boundary --no-cpu-baseline || exit 1
+  b c3d --steps 20 --warmup 5 --no-boundary --no-cpu-baseline --full || exit 1
+  b c3d_q8 --steps 20 --warmup 5 --no-boundary --no-cpu-baseline --hw-queues 8 --no-setup --full || exit 1
+  b c5s $C5 --steps 6 --warmup 3 --no-boundary --no-cpu-baseline --full || exit 1
   timeout -k 10 300 python scripts/n8_floor.py > gpurun_out/${TAG}_n8_floor.json 2> gpurun_out/${TAG}_n8_floor.err || { tail -5 gpurun_out/${TAG}_n8_floor.err; exit 1; }
   cat gpurun_out/${TAG}_n8_floor.json
   python3 -c "import json,sys; [print(n, json.dumps(json.load(open(f'gpurun_out/${TAG}_bench_'+n+'.json')).get('setup'))) for n in ('c3d','c5s')]" ;;
 bench)
   make -C oracle > /dev/null || exit 1
   timeout -k 10 200 python scripts/cpu_config1.py > gpurun_out/${TAG}_cfg1.json && cat gpurun_out/${TAG}_cfg1.json || exit 1
-  b c3d --steps 20 --warmup 5 --no-boundary --no-cpu-baseline || exit 1
-  b c3 || exit 1
-  b c2 $C2 --no-cpu-baseline || exit 1
-  b c4 --size 8192 --no-cpu-baseline --no-boundary || exit 1
-  b c5 $C5 --steps 10 --warmup 4 --no-boundary --cpu-seconds 10 || exit 1 ;;
+  b c3d --steps 20 --warmup 5 --no-boundary --no-cpu-baseline --full || exit 1
+  b c3 --full || exit 1
+  b c2 $C2 --no-cpu-baseline --full || exit 1
+  b c4 --size 8192 --no-cpu-baseline --no-boundary --full || exit 1
+  b c5 $C5 --steps 10 --warmup 4 --no-boundary --cpu-seconds 10 --full || exit 1 ;;
 prof3)
   bash scripts/profile.sh prof_${TAG}_c3 > gpurun_out/prof_${TAG}_c3.log 2>&1 || { tail -20 gpurun_out/prof_${TAG}_c3.log; exit 1; }
   python3 scripts/pmc_summary.py gpurun_out/prof_${TAG}_c3 gpurun_out/${TAG}_c3_pmc.json s64-4096x4096-d5-exact-f32-n1 20 20 > gpurun_out/${TAG}_c3_pmc.txt || exit 1

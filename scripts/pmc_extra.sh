@@ -6,7 +6,7 @@ TAG=${1:-pmcx}; shift || true
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="bench.py --steps 20 --warmup 10 --iso 20 --settle 0 --no-cpu-baseline --no-boundary --no-setup $*"
+BENCH="bench.py --full --steps 20 --warmup 10 --iso 20 --settle 0 --no-cpu-baseline --no-boundary --no-setup $*"
 i=0
 for P in "SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_LDS_UNALIGNED_STALL SQ_INST_LEVEL_LDS" \
          "SQC_DCACHE_MISSES SQC_ICACHE_MISSES SQ_IFETCH SQ_INST_LEVEL_SMEM SQ_INST_LEVEL_VMEM SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES"; do

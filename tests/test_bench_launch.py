@@ -68,6 +68,19 @@ def test_hw_queues_flag(monkeypatch, gpus, flag, want):
     assert os.environ["GPU_MAX_HW_QUEUES"] == want
 
 
+def test_dump_rows_are_fixed_and_bounded():
+    """--dump-outputs: a frame that fits is written whole; a larger one as the same ascending choice
+    of distinct rows every time, within the size bound."""
+    import numpy as np
+    assert np.array_equal(bench.dump_rows(48, 64 * 12), np.arange(48))
+    row_bytes = 4096 * 12
+    a, b = bench.dump_rows(4096, row_bytes), bench.dump_rows(4096, row_bytes)
+    assert np.array_equal(a, b)
+    assert len(a) == bench.DUMP_MAX_BYTES // row_bytes and len(a) * row_bytes <= 64 << 20
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 4096
+    assert len(bench.dump_rows(4096, 2 * row_bytes)) == len(a) // 2  # an f64 framebuffer: half the rows
+
+
 def test_priorities_parser():
     assert bench.parse_priorities("0,-1,0") == [0, -1, 0]
     for bad in ("", "1", "0,x", "-2"):
