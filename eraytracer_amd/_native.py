@@ -31,6 +31,9 @@ RT_CFG_CULL = 3
 RT_KT_PRIMARY, RT_KT_LEVEL1, RT_KT_RENDER, RT_KT_PMASK = 1, 2, 4, 8
 RT_LEVELS_HIT = 1
 RT_ENGINE_WAVE, RT_ENGINE_FUSED = 0, 1
+# enum rt_eval_op (rt_eval_math, diagnostic)
+(RT_EVAL_POW, RT_EVAL_POW_GENERAL, RT_EVAL_SQRT, RT_EVAL_DIV, RT_EVAL_NORMALIZE3, RT_EVAL_DIV_DIM,
+ RT_EVAL_IDIV_DIM) = range(7)
 
 # every symbol include/rt_mi355x.h declares (tests/test_boundary.py checks the export list)
 EXPORTS = (
@@ -39,6 +42,7 @@ EXPORTS = (
     "rt_update_scene",
     "rt_ppm_bound", "rt_ppm_format", "rt_render_ppm_file",
     "rt_slab_header_bytes", "rt_slab_pack", "rt_slab_unpack", "rt_selftest_math",
+    "rt_eval_math",
     "rt_host_alloc", "rt_host_free", "rt_reset_contexts", "rt_kernel_time", "rt_engine",
 )
 
@@ -143,6 +147,7 @@ def lib() -> ctypes.CDLL:
     L.rt_configure.argtypes = [vp, i32, ctypes.c_int64]
     L.rt_engine.argtypes = [vp, u32]
     L.rt_selftest_math.argtypes = [i32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    L.rt_eval_math.argtypes = [i32, i32, ctypes.c_uint64, vp, vp, vp, ctypes.c_int32, vp]
     L.rt_slab_header_bytes.restype = ctypes.c_size_t
     L.rt_slab_header_bytes.argtypes = [u32, u32, u32, u32]
     L.rt_slab_pack.argtypes = [vp, u32, u32, u32, u32, u32, i32, vp, vp, vp]

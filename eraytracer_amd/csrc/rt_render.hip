@@ -174,12 +174,26 @@ __device__ __forceinline__ double max0(double x) { return x > 0 ? x : 0.0; } // 
 
 // math:pow/2 (:289) is the host libm's pow, which is correctly rounded for all but
 // vanishingly rare arguments.  For the small non-negative integer exponents scenes use
-// (specular_power 1, 4, 20) the kernel evaluates x^n by binary powering in double-double
-// arithmetic (~2^-100 relative error, then one rounding), which gives the correctly
-// rounded result — cheaper than, and closer to libm than, the device's general pow.  The
-// pairs hi + lo are kept unnormalised (|lo| stays within ~2 ulp(hi), the product's exact
-// low part plus the cross terms), so a step is one product and its fma error terms; the fma
-// calls are error-free product transformations, not contractions.
+// (specular_power 1, 4, 20; any integer 0..1024 takes this path) the kernel evaluates x^n by
+// binary powering in double-double arithmetic, then one rounding — cheaper than, and closer to
+// libm than, the device's general pow.  The pairs hi + lo are kept unnormalised, so a step is
+// one product and its fma error terms; the fma calls are error-free product transformations, not
+// contractions.  lo is the product's exact low part plus the cross terms, and a squaring doubles
+// lo / hi: after k squarings |lo| is up to ~2^k ulp(hi) (2^-43 hi for n = 1024, not a fixed
+// ~2 ulp), and the dropped lo^2 and lo lo' terms leave a relative error of ~2^-100 for the
+// exponents scenes use (n <= 20) growing to ~2^-86 at n = 1024.  That is far inside half an ulp,
+// so the result is the correctly rounded one unless x^n lies within that distance of a rounding
+// boundary (about one operand in 2^33 at n = 1024): tests/test_gpu_math_exact.py compares it bit for
+// bit with exact integer arithmetic for every n in 0..1024 (and tests/test_exact_ref.py restates
+// it on the CPU).  That holds for results >= 2^-969 and for results that round to 0.  Below
+// 2^-969 a pair's low part is itself subnormal, so the fma error terms are rounded, and in the
+// subnormal band hi + lo is a second rounding: there the result is within one unit in the last
+// place (2^-1074 in the subnormal band) of the correctly rounded value, and differs from it for
+// ~2 % of the operands in [2^-1022, 2^-969) and ~5 % of the subnormal ones; the oracle's glibc
+// pow is the correct one there.  (At most 2^-1022 in a highlight term: invisible next to the 1e-5
+// bar.  A repair — redo such lanes from x scaled into [0.75, 1.5), round once at the result's
+// quantum — gave the exact bits but cost config 3 2 % by its mere presence in the shading
+// kernels, registers and SGPR spills: profiles/pow_tiny_ab.txt.)
 __device__ __forceinline__ void dd_sqr(double &h, double &l) {
     const double p = h * h;
     const double e = __builtin_fma(h + h, l, __builtin_fma(h, h, -p));
@@ -1662,6 +1676,35 @@ __global__ __launch_bounds__(256) void k_selftest_math(unsigned long long n, uns
     if (local) atomicAdd(bad, local);
 }
 
+// rt_eval_math: one operand per work-item in array order (elements 64k .. 64k+63 are one wave, so
+// the caller's operand order decides what is wave-uniform), through the functions the render
+// kernels call.  dim reaches div_dim / idiv_dim as a kernel argument (wave-uniform, as W, H and
+// the row block are at their call sites).
+template <int OP>
+__global__ __launch_bounds__(256) void k_eval_math(unsigned long long n, const double *__restrict__ a,
+                                                   const double *__restrict__ b,
+                                                   const unsigned char *__restrict__ act, int dim,
+                                                   double *__restrict__ out) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (OP == RT_EVAL_NORMALIZE3) {
+        const D3 u = normalize3(D3{a[3 * i], a[3 * i + 1], a[3 * i + 2]}, false);
+        out[3 * i] = u.x;
+        out[3 * i + 1] = u.y;
+        out[3 * i + 2] = u.z;
+        return;
+    }
+    const double x = a[i];
+    double r;
+    if (OP == RT_EVAL_POW) r = pow_libm<false>(x, b[i], act ? act[i] != 0 : true);
+    else if (OP == RT_EVAL_POW_GENERAL) r = pow_libm<true>(x, b[i]);
+    else if (OP == RT_EVAL_SQRT) r = sqrt_x<false>(x);
+    else if (OP == RT_EVAL_DIV) r = div_n(x, b[i]);
+    else if (OP == RT_EVAL_DIV_DIM) r = div_dim(x, dim);
+    else r = (double)idiv_dim((int)x, dim);
+    out[i] = r;
+}
+
 } // namespace
 
 // =====================================================================================
@@ -1865,6 +1908,55 @@ int rt_selftest_math(int device, uint64_t n, uint64_t seed, uint64_t *mismatches
         *mismatches = h;
     }
     (void)hipFree(d);
+    return rc;
+}
+
+int rt_eval_math(int device, int op, uint64_t n, const double *a, const double *b, const uint8_t *act,
+                 int32_t dim, double *out) {
+    if (!a || !out || n == 0 || op < RT_EVAL_POW || op > RT_EVAL_IDIV_DIM) return RT_EBADARG;
+    const bool two = op == RT_EVAL_POW || op == RT_EVAL_POW_GENERAL || op == RT_EVAL_DIV;
+    if (two && !b) return RT_EBADARG;
+    if ((op == RT_EVAL_DIV_DIM || op == RT_EVAL_IDIV_DIM) && (dim < 1 || dim > (1 << 20))) return RT_EBADARG;
+    if (n > (1ull << 26)) return RT_ETOOBIG;
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) return RT_ENODEV;
+    DevGuard g(device);
+    const size_t per = op == RT_EVAL_NORMALIZE3 ? 3 : 1, bytes = (size_t)n * per * sizeof(double);
+    double *d_a = nullptr, *d_b = nullptr, *d_out = nullptr;
+    unsigned char *d_act = nullptr;
+    int rc = RT_OK;
+    if (hipMalloc(&d_a, bytes) != hipSuccess || hipMalloc(&d_out, bytes) != hipSuccess ||
+        (two && hipMalloc(&d_b, bytes) != hipSuccess) ||
+        (op == RT_EVAL_POW && act && hipMalloc(&d_act, (size_t)n) != hipSuccess))
+        rc = RT_ENOMEM;
+    if (rc == RT_OK && (hipMemcpy(d_a, a, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+                        (d_b && hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice) != hipSuccess) ||
+                        (d_act && hipMemcpy(d_act, act, (size_t)n, hipMemcpyHostToDevice) != hipSuccess)))
+        rc = RT_EHIP;
+    if (rc == RT_OK) {
+        const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+#define RT_EVAL_CASE(OP)                                                                                           \
+    case OP:                                                                                                       \
+        hipLaunchKernelGGL(k_eval_math<OP>, grid, blk, 0, nullptr, (unsigned long long)n, d_a, d_b, d_act, (int)dim, \
+                           d_out);                                                                                 \
+        break;
+        switch (op) {
+            RT_EVAL_CASE(RT_EVAL_POW)
+            RT_EVAL_CASE(RT_EVAL_POW_GENERAL)
+            RT_EVAL_CASE(RT_EVAL_SQRT)
+            RT_EVAL_CASE(RT_EVAL_DIV)
+            RT_EVAL_CASE(RT_EVAL_NORMALIZE3)
+            RT_EVAL_CASE(RT_EVAL_DIV_DIM)
+            RT_EVAL_CASE(RT_EVAL_IDIV_DIM)
+        }
+#undef RT_EVAL_CASE
+        if (hipGetLastError() != hipSuccess || hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = RT_EHIP;
+    }
+    (void)hipFree(d_a);
+    (void)hipFree(d_b);
+    (void)hipFree(d_out);
+    (void)hipFree(d_act);
     return rc;
 }
 

@@ -339,7 +339,10 @@ int rt_slab_unpack(const void *const *d_headers, const void *const *d_values, ui
         sp.vals[s] = d_values[s];
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (width % UNPACK_PX == 0) { // 4 pixels per thread, 16-byte stores
+    // 4 pixels per thread, 16-byte stores: every row of a 16-byte aligned image starts on a multiple
+    // of 16 bytes (4 pixels are 48 or 96 bytes); any other image (a view into a larger buffer)
+    // takes the element-wise kernel
+    if (width % UNPACK_PX == 0 && (reinterpret_cast<uintptr_t>(d_image) & 15) == 0) {
         const uint32_t ncol = (width + SLAB_BLOCK * UNPACK_PX - 1) / (SLAB_BLOCK * UNPACK_PX);
         const uint64_t nblocks = (uint64_t)ncol * height;
         if (nblocks >= (1ull << 31)) return RT_ETOOBIG;

@@ -166,6 +166,34 @@ int rt_device_count(int *count);
  * operands; *mismatches = the count of differing results (0 expected). */
 int rt_selftest_math(int device, uint64_t n, uint64_t seed, uint64_t *mismatches);
 
+/* Diagnostic (test-only ABI like rt_selftest_math; no render path calls it, and it may change
+ * with the kernels' internals): evaluate one of the kernels' arithmetic primitives on host
+ * arrays of binary64 operands, one operand per work-item in array order, 256 work-items per
+ * workgroup — elements 64k .. 64k+63 form one wave, so the caller's operand order decides
+ * which of the primitives' wave-uniform paths run.  Results go back to host arrays.
+ *   RT_EVAL_POW          out[i] = pow_libm<false>(a[i], b[i], act[i]); act (optional, n bytes):
+ *                        lanes with act[i] = 0 are the shading's inactive lanes, whose out[i] is
+ *                        unspecified.  b[i] must be an integer in [0, 1024] (the host's guarantee
+ *                        for kernels built without the general pow).
+ *   RT_EVAL_POW_GENERAL  out[i] = pow_libm<true>(a[i], b[i]): any b
+ *   RT_EVAL_SQRT         out[i] = sqrt_x<false>(a[i])
+ *   RT_EVAL_DIV          out[i] = div_n(a[i], b[i]): no range handling, see rt_render.hip
+ *   RT_EVAL_NORMALIZE3   a and out hold n vectors (3n values): out = normalize3(a, false)
+ *   RT_EVAL_DIV_DIM      out[i] = div_dim(a[i], dim), 1 <= dim <= 2^20 (one scalar per call)
+ *   RT_EVAL_IDIV_DIM     out[i] = idiv_dim((int)a[i], dim), a[i] an integer in [0, 2^31)
+ * b is read by the first, second and fourth operation only; n <= 2^26. */
+enum rt_eval_op {
+    RT_EVAL_POW = 0,
+    RT_EVAL_POW_GENERAL = 1,
+    RT_EVAL_SQRT = 2,
+    RT_EVAL_DIV = 3,
+    RT_EVAL_NORMALIZE3 = 4,
+    RT_EVAL_DIV_DIM = 5,
+    RT_EVAL_IDIV_DIM = 6
+};
+int rt_eval_math(int device, int op, uint64_t n, const double *a, const double *b, const uint8_t *act,
+                 int32_t dim, double *out);
+
 /* Validate a scene list without rendering (0 = a scene the reference would
  * trace without crashing for a pixel that hits any object). */
 int rt_scene_check(const rt_elem *scene, uint32_t n_elems);
@@ -280,7 +308,14 @@ int rt_kernel_time(rt_prepared *p, int kernel, double *total_ms, uint64_t *launc
  *   pixel (shard_rows*width*3 elements) in the worst case.
  * rt_slab_unpack: decode nshards (<= RT_MAX_SHARDS) shards into the row-major image
  *   ([H][W*3]) on `stream` — rt_unshard fused with the decode; d_headers[s] / d_values[s]
- *   are device pointers to shard s's header and values. */
+ *   are device pointers to shard s's header and values.
+ * Alignment: a header must be 8-byte aligned (its u64 count and mask words; the mask offset is a
+ *   multiple of 256), a slab, a values buffer and d_image aligned to their element (4 bytes for
+ *   RT_OUT_F32, 8 for RT_OUT_F64).  A 16-byte aligned d_image whose width is a multiple of 4 is
+ *   written with 16-byte stores; any other one element by element (slower, same bytes).
+ * A pack owns its header and values buffers until its kernels have run: the block offsets are
+ *   scanned in place in the header, so two packs in flight (on different streams) must not share
+ *   a header or a values buffer, and neither may be read before the pack's stream reaches it. */
 #define RT_MAX_SHARDS 64
 size_t rt_slab_header_bytes(uint32_t width, uint32_t height, uint32_t row_block, uint32_t nshards);
 int rt_slab_pack(const void *d_slab, uint32_t width, uint32_t height, uint32_t row_block, uint32_t shard,

@@ -409,27 +409,48 @@ def test_launch_writes_only_image_rows(name, spp):
 
 
 # ---- compact slab transfer (rt_slab_pack / rt_slab_unpack; dist.CompactGather) ----------
-@pytest.mark.parametrize("prec", ["f32", "f64"])
-@pytest.mark.parametrize("w,h,rb,ns", [(80, 70, 16, 3), (64, 64, 16, 1), (33, 17, 4, 2), (100, 9, 16, 8),
-                                       (257, 31, 5, 4), (2052, 40, 16, 8), (1024, 33, 7, 3)])
+# k_scan (rt_slab.hip) scans the per-block counts in tiles of 8192 (2,097,152 slab pixels) with a
+# carry between tiles.  One shard, rb = 16: 2048x1024 is exactly one full tile (nblk = 8192);
+# 2049x1024 one count past it (nblk = 8196; a width that is no multiple of 4: k_unpack);
+# 4100x1030 three tiles (1040 slab rows with padding, nblk = 16,657; k_unpack4 with two column
+# groups, the second partial).
+SLAB_SHAPES = [(80, 70, 16, 3), (64, 64, 16, 1), (33, 17, 4, 2), (100, 9, 16, 8), (257, 31, 5, 4), (2052, 40, 16, 8),
+               (1024, 33, 7, 3)]
+SLAB_CASES = [s + (p,) for p in ("f32", "f64") for s in SLAB_SHAPES] + [
+    (2048, 1024, 16, 1, "f32"), (2049, 1024, 16, 1, "f32"), (4100, 1030, 16, 1, "f32"), (4100, 1030, 16, 1, "f64")]
+SCAN_TILE_PX = 8192 * 256
+
+
+@pytest.mark.parametrize("w,h,rb,ns,prec", SLAB_CASES)
 def test_slab_codec_matches_reference_format(prec, w, h, rb, ns):
     """HIP pack gives the header and values of the test-side restatement byte for byte, on
     random sparse slabs (-0.0 and NaN payloads count as non-zero; padding rows hold garbage);
     HIP unpack reassembles the frame exactly."""
     import torch
 
-    from eraytracer_amd.dist import SlabCodec, shard_global_rows
-    from tests.slab_ref import RefCodec
     dt = torch.float32 if prec == "f32" else torch.float64
-    codec, ref = SlabCodec(w, h, rb, ns, prec), RefCodec(w, h, rb, ns)
-    assert codec.header_bytes == ref.header_bytes
-    rows = N.lib().rt_shard_rows(h, rb, ns)
     gen = torch.Generator().manual_seed(w * 1000 + h * 10 + ns)
     frame = torch.rand((h, w, 3), generator=gen, dtype=torch.float64).to(dt)
     frame[torch.rand((h, w), generator=gen) < 0.7] = 0.0
     frame[0, 0] = torch.tensor([0.0, -0.0, 0.0], dtype=dt)
     frame[h - 1, w - 1, 2] = float("nan")
-    hdrs, vals = [], []
+    _slab_round_trip(frame, rb, ns, prec)
+
+
+def _slab_round_trip(frame, rb, ns, prec):
+    """Pack every shard of `frame` with the HIP codec and with RefCodec (count, offsets, mask and
+    values byte for byte), decode with the HIP codec (the frame bit for bit); returns the
+    reference headers."""
+    import torch
+
+    from eraytracer_amd.dist import SlabCodec, shard_global_rows
+    from tests.slab_ref import RefCodec
+    h, w = frame.shape[:2]
+    dt = frame.dtype
+    codec, ref = SlabCodec(w, h, rb, ns, prec), RefCodec(w, h, rb, ns)
+    assert codec.header_bytes == ref.header_bytes
+    rows = N.lib().rt_shard_rows(h, rb, ns)
+    hdrs, vals, ref_hdrs = [], [], []
     for s in range(ns):
         g = shard_global_rows(h, rb, ns, s)
         slab = torch.full((rows, w, 3), 5.0, dtype=dt)
@@ -451,11 +472,75 @@ def test_slab_codec_matches_reference_format(prec, w, h, rb, ns):
         assert torch.equal(vd.cpu()[: 3 * n].view(bits), vr[: 3 * n].view(bits))
         hdrs.append(hd)
         vals.append(vd)
+        ref_hdrs.append(hr)
     img = torch.full((h, w, 3), 3.0, dtype=dt, device="cuda")
     codec.unpack(hdrs, vals, img)
     torch.cuda.synchronize()
     bits = torch.int32 if prec == "f32" else torch.int64
     assert torch.equal(img.cpu().view(bits), frame.view(bits))
+    return ref_hdrs
+
+
+@pytest.mark.parametrize("content", ["zero", "full", "first_tile", "last_tile"])
+@pytest.mark.parametrize("w,h,prec", [(2049, 1024, "f32"), (64, 64, "f32"), (64, 64, "f64")])
+def test_slab_codec_frame_content(w, h, prec, content):
+    """The codec on frames whose non-zero pixels are nowhere, everywhere, or only in the first or
+    only in the last of k_scan's tiles of 8192 block counts (2049x1024: pixels below / from
+    2,097,152; a one-tile frame: its first / second half): a carry that is dropped or applied
+    twice changes the clustered frames' offsets and count.  One shard, rb = 16."""
+    import torch
+
+    dt = torch.float32 if prec == "f32" else torch.float64
+    px = w * h
+    nblk = -(-px // 256)
+    split = (nblk - 1) // 8192 * SCAN_TILE_PX or px // 2  # the last tile's first pixel
+    gen = torch.Generator().manual_seed(w + h)
+    flat = torch.zeros((px, 3), dtype=dt)
+    lo, hi = {"zero": (0, 0), "full": (0, px), "first_tile": (0, split), "last_tile": (split, px)}[content]
+    flat[lo:hi] = (torch.rand((hi - lo, 3), generator=gen, dtype=torch.float64) + 0.5).to(dt)
+    (hr,) = _slab_round_trip(flat.reshape(h, w, 3), 16, 1, prec)
+    count = int(hr[:8].view(torch.int64)[0])
+    off = hr[64:64 + 4 * nblk].view(torch.int32).to(torch.int64)
+    blk0 = torch.arange(nblk, dtype=torch.int64) * 256
+    assert count == hi - lo
+    assert torch.equal(off, (blk0.clamp(lo, hi) - lo))  # 0 ("zero"), 256 i ("full"), clipped to the cluster
+
+
+def test_slab_unpack_into_an_unaligned_view():
+    """rt_slab_unpack into an image that starts 4 bytes into a larger device buffer (a width that is
+    a multiple of 4, which an aligned image decodes with 16-byte stores): the same frame as the
+    aligned decode, and the words on both sides of the view keep their guard value.  (rt_slab_unpack
+    sends such an image to the element-wise kernel.  Whether 16-byte stores to it would go wrong
+    depends on the device's unaligned-access mode; this pins the result either way.)"""
+    import torch
+
+    from eraytracer_amd.dist import SlabCodec, shard_global_rows
+    w, h, rb, ns = 64, 48, 16, 2
+    codec = SlabCodec(w, h, rb, ns, "f32")
+    rows = N.lib().rt_shard_rows(h, rb, ns)
+    gen = torch.Generator().manual_seed(6448)
+    frame = torch.rand((h, w, 3), generator=gen, dtype=torch.float32)
+    frame[torch.rand((h, w), generator=gen) < 0.6] = 0.0
+    hdrs, vals = [], []
+    for s in range(ns):
+        g = shard_global_rows(h, rb, ns, s)
+        slab = torch.zeros((rows, w, 3), dtype=torch.float32)
+        slab[torch.from_numpy(g >= 0)] = frame[torch.from_numpy(g[g >= 0])]
+        hdrs.append(torch.empty(codec.header_bytes, dtype=torch.uint8, device="cuda"))
+        vals.append(torch.empty(rows * w * 3, dtype=torch.float32, device="cuda"))
+        codec.pack(slab.cuda(), s, hdrs[-1], vals[-1])
+    n, guard = h * w * 3, 7.5
+    buf = torch.full((n + 9,), guard, dtype=torch.float32, device="cuda")
+    view = buf[1:1 + n]
+    aligned = torch.full((n,), guard, dtype=torch.float32, device="cuda")
+    assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 4 and aligned.data_ptr() % 16 == 0
+    codec.unpack(hdrs, vals, view)
+    codec.unpack(hdrs, vals, aligned)
+    torch.cuda.synchronize()
+    out = buf.cpu()
+    assert torch.equal(out[1:1 + n].view(torch.int32), aligned.cpu().view(torch.int32))
+    assert torch.equal(aligned.cpu().view(torch.int32), frame.reshape(-1).view(torch.int32))
+    assert bool((out[:1] == guard).all()) and bool((out[1 + n:] == guard).all())
 
 
 def test_compact_gather_of_rendered_shards(oracle):
