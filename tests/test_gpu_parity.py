@@ -355,6 +355,35 @@ def test_ppm_gpu_range_error():
         ppm_text_gpu(img)
 
 
+@pytest.mark.parametrize("w,h,dtype", [(600, 450, np.float64), (600, 450, np.float32), (2623, 100, np.float64),
+                                      (61, 37, np.float32)])
+def test_ppm_gpu_many_blocks_and_binary32(tmp_path, w, h, dtype):
+    """rt_ppm_format on frames of more than 1,024 blocks of 256 pixels (600x450: 1,055 blocks, so
+    k_ppm_scan's threads take two block sums each and its tail threads none; 2623x100: 1,025 blocks,
+    the last one partial) and on binary32 frames (formatted from the float values), random values
+    in [-2, 3] with +inf (prints MaxValue) among them: the Python writer's bytes."""
+    from eraytracer_amd.raytracer import ppm_text_gpu
+    rng = np.random.default_rng(w * 1000 + h)
+    img = rng.uniform(-2.0, 3.0, size=(h, w, 3)).astype(dtype)
+    img[0, 0, 1] = img[h // 2, w // 3, 2] = img[h - 1, w - 1, 0] = np.inf
+    assert -(-w * h // 256) > 1024 or dtype == np.float32
+    got, want = ppm_text_gpu(img), _py_ppm(tmp_path, img)
+    assert len(got) == len(want)
+    assert got == want
+    assert want.split(b"\n", 3)[3].split()[1] == b"255"  # the +inf channel
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("-inf")])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_ppm_gpu_nan_and_minus_inf_are_range_errors(bad, dtype):
+    from eraytracer_amd.raytracer import ppm_text_gpu
+    img = np.full((5, 7, 3), 0.5, dtype=dtype)
+    img[3, 4, 1] = bad
+    with pytest.raises(N.RtError) as ei:
+        ppm_text_gpu(img)
+    assert ei.value.code == N.RT_ERANGE
+
+
 def test_render_ppm_file_matches_golden_and_python(tmp_path, oracle):
     """rt_render_ppm_file (raytrace/5 with the P3 text made on the GPU) reproduces the
     committed run.sh / run-concurrent.sh P3 fixtures and the Python writer on the oracle's
