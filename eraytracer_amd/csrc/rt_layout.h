@@ -1,6 +1,6 @@
 // rt_layout.h — the "compiled scene": how a reference scene list (raytracer.erl:618-665)
 // lives in HBM for the render kernel.  Shared by the host scene compiler (rt_scene.cpp)
-// and the kernel (rt_render.hip).
+// and the kernels (rt_render.hip and its fragments).
 //
 // The reference scans the scene list in order, dispatching on the record tag of every
 // element (nearest_object_intersecting_ray/6, raytracer.erl:303-346; ray_object_intersect/2,
@@ -28,14 +28,14 @@ constexpr int PL_W = 4;      // nx ny nz distance
 constexpr int PL_ORG_W = 1;  // V0 = -(N.O + distance)          (:465-466)
 constexpr int OBJ_W = 12;    // n(3) or centre(3), colour(3), specular_power, shininess, reflectivity, pad
 constexpr int LIGHT_W = 12;  // diffuse(3), location(3), specular(3), pad(3)
-// wave culling (see rt_render.hip, "Beam culling"): sphere bounds and, per tabled origin, the
+// wave culling (see rt_cull.inc, "Beam culling"): sphere bounds and, per tabled origin, the
 // sphere's direction cone as seen from that origin with conservative margins applied
 constexpr int SPH_B_W = 4;   // cx cy cz r
 constexpr int SPH_OB_W = 8;  // vx vy vz (= c - o), |v|, sin(rho) upper bound, cos(rho) lower bound, near(0/1),
                              // lower bound of |v| - r (no ray from o reaches the sphere before that distance)
 
 constexpr int SPH_OB32_W = 8; // floats
-constexpr float BEAM32_EPS = 1.0e-5f; // binary32 beams' margin (rt_render.hip, "Binary32 beams")
+constexpr float BEAM32_EPS = 1.0e-5f; // binary32 beams' margin (rt_cull.inc, "Binary32 beams")
 
 // Culling is exact only while every binary64 rounding error in the reference's sphere test is
 // far below its 0.001 discriminant threshold: all scene coordinates within this bound.
@@ -48,10 +48,7 @@ constexpr int OBJ_META_W = 4; // kind, local index within its type, canon compac
 
 // Shadow rays from a light into the cone around a target sphere are split into OCC_CELLS
 // direction cells (occ_cell); each cell has its own, smaller, occluder mask.
-#ifndef RT_OCC_CELLS
-#define RT_OCC_CELLS 16 // 4: signs only; 1: one mask per (light, target), as before the cells
-#endif
-constexpr int OCC_CELLS = RT_OCC_CELLS;
+constexpr int OCC_CELLS = 16; // per axis: the sign, and |sd - a| against half the cone's sine
 constexpr float OCC_CELL_EPS = 1.0e-4f; // cells overlap by this much (unit-vector components)
 constexpr int OCC_CELLS_MIN_SPHERES = 128; // smaller scenes keep one cell
 // Occluder masks cost the host one test per (light, target, sphere) triple: above this many the
@@ -62,7 +59,7 @@ constexpr double OCC_MAX_BYTES = 64.0 * 1024 * 1024;
 
 constexpr int LDS_STAGE_MAX = 32 * 1024; // 5 workgroups per CU keep their 32 KiB each
 
-// Sphere BVH for incoherent reflection rays (see rt_render.hip, "Per-lane BVH"): a binary tree
+// Sphere BVH for incoherent reflection rays (see rt_cull.inc, "Per-lane BVH"): a binary tree
 // over the spheres, built on the host by SAH splits (depth <= ceil(log2 n_sph) + 2); one 64-byte
 // node holds both children's binary32 boxes (rounded outwards and inflated, so the box test
 // never rejects a sphere the binary64 test accepts), their links (>= 0: node, < 0: ~sphere) and,
@@ -111,7 +108,7 @@ struct SceneHdr {
     // nodes and the sphere rows (o_sph) staged there (l_bvh = -1: read from HBM) and of each
     // lane's stack (l_stack).
     int bvh_ok, o_bvh, n_bvh, bvh_level, bvh_depth, l_bvh, l_bsph, l_stack;
-    // Range checks of normalize3 (rt_render.hip) proven unnecessary on the host for this scene:
+    // Range checks of normalize3 (rt_math.inc) proven unnecessary on the host for this scene:
     // norm_ok — spheres only, within CULL_EXTENT, every |radius| >= 1e-50 and every light off every
     // sphere's surface (| |L - c| - |r| | > 1e-9 (ext + 1)): the surface normals (hit - c) and the
     // light directions (L - hit) have squared lengths inside [2^-400, 2^400]; prim_ok — the same

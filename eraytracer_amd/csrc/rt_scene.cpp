@@ -679,27 +679,16 @@ int compile_scene(const rt_elem *in, uint32_t n, Compiled &out) {
                         if (bot - 1e-7 > s * a3[k] + t_hi + eps) return false;
                         return true;
                     };
-                    // the kernel's bins along one axis (occ_cell): the sign of dir_k - a_k and, with
-                    // 16 cells, |dir_k - a_k| below / above tau; with 64, below tau/2, tau, 3 tau/2 or above
+                    // the kernel's bins along one axis (occ_cell): the sign of dir_k - a_k and
+                    // |dir_k - a_k| below / above tau
                     auto bin = [&](int b, double &s, double &t_lo, double &t_hi) {
                         const double inf = 1e300;
-                        if (ncell == 4) {
-                            s = (b & 1) ? 1.0 : -1.0; t_lo = 0; t_hi = inf;
-                        } else if (ncell == 16) {
-                            s = (b & 1) ? 1.0 : -1.0;
-                            t_lo = (b & 2) ? tau : 0.0; t_hi = (b & 2) ? inf : tau;
-                        } else {
-                            s = (b & 4) ? 1.0 : -1.0;
-                            const int g = b & 3;
-                            t_lo = g * 0.5 * tau; t_hi = g == 3 ? inf : (g + 1) * 0.5 * tau;
-                        }
+                        s = (b & 1) ? 1.0 : -1.0;
+                        t_lo = (b & 2) ? tau : 0.0; t_hi = (b & 2) ? inf : tau;
                     };
-                    for (int c = 0; c < ncell; c++) {
+                    for (int c = 0; c < ncell; c++) { // (ncell is OCC_CELLS or 1)
                         // cell -> the bins of axes i and j (occ_cell's numbering)
-                        int bi = 0, bj = 0;
-                        if (ncell == 4) { bi = c & 1; bj = (c >> 1) & 1; }
-                        else if (ncell == 16) { bi = (c & 1) | ((c >> 1) & 2); bj = ((c >> 1) & 1) | ((c >> 2) & 2); }
-                        else { bi = c & 7; bj = c >> 3; }
+                        const int bi = (c & 1) | ((c >> 1) & 2), bj = ((c >> 1) & 1) | ((c >> 2) & 2);
                         double si, li, hi_, sj, lj, hj;
                         bin(bi, si, li, hi_);
                         bin(bj, sj, lj, hj);

@@ -672,10 +672,8 @@ __device__ __forceinline__ D3 shade_bits(const Scene &S, int id, const D3 &d, co
 // level lv carried up its parent links to the pixel, each ancestor reshaded with its child's
 // colour and its shadow answers, which sit in its child's record (pb: those of the record one
 // level up; a record's pbits word is its parent's).  Lanes off the walk (on false) follow the lead
-// lane's chain, so every read is of a valid record.
-#ifndef RT_WALK_PREFETCH
-#define RT_WALK_PREFETCH 0 // 1: config 5 -3 %, config 3 and small shards neutral (profiles/r06p_ab_walk_prefetch.txt)
-#endif
+// lane's chain, so every read is of a valid record.  (Loading the next ancestor's record before the
+// current one is shaded: config 5 -3 %, config 3 and small shards neutral, profiles/r06p_ab_walk_prefetch.txt)
 template <int PREC, bool GENPOW, int SPH>
 __device__ __forceinline__ void walk_up(const Scene &S, const PassGeom &g, const HitRec *__restrict__ q,
                                         size_t level_slots, int lv, D3 c, int parent, unsigned pb, int pix, bool on,
@@ -683,38 +681,6 @@ __device__ __forceinline__ void walk_up(const Scene &S, const PassGeom &g, const
     const unsigned long long m = __ballot(on);
     if (m == 0) return;
     const int lead = __builtin_ctzll(m);
-#if RT_WALK_PREFETCH // A/B builds: the next ancestor's record loaded before the current one is shaded
-    auto slot_of = [&](int link) {
-        const int lp = __builtin_amdgcn_readlane(link, lead);
-        const int ps = on ? link : lp;
-        return (unsigned)ps < (unsigned)level_slots ? ps : 0;
-    };
-    auto raw = [&](int k, int ps) { // level 0: the 16-byte Rec0 (rebuilt when used)
-        HitRec r;
-        if (k == 0) {
-            const Rec0 r0 = reinterpret_cast<const Rec0 *>(q)[ps];
-            r.pix = r0.pix; r.obj = r0.obj; r.hx = r0.t; r.parent = -1; r.pbits = 0;
-            r.hy = r.hz = r.dx = r.dy = r.dz = 0.0;
-        } else {
-            r = q[(size_t)k * level_slots + ps];
-        }
-        return r;
-    };
-    HitRec cur = raw(lv - 1, slot_of(parent));
-    for (int k = lv - 1; k >= 0; --k) { // (wave-uniform: one level per step)
-        HitRec nxt = cur;
-        if (k > 0) nxt = raw(k - 1, slot_of(cur.parent));
-        HitRec r = cur;
-        if (k == 0) r = rec0_to_rec(S.h, g, Rec0{cur.pix, cur.obj, cur.hx});
-        const D3 h = {r.hx, r.hy, r.hz};
-        c = shade_bits<GENPOW, SPH>(S, r.obj, D3{r.dx, r.dy, r.dz}, h, hit_normal<SPH>(S, r.obj, h), c,
-                                    obj_row<SPH>(S, r.obj)[8], pb);
-        pb = (unsigned)cur.pbits;
-        cur = nxt;
-    }
-    if (on) put_pixel<PREC>(out, g, (size_t)pix, c);
-    return;
-#endif
     for (int k = lv - 1; k >= 0; --k) { // (wave-uniform: one level per step)
         RT_LINK_CHECK(!on || (unsigned)parent < (unsigned)level_slots,
                       "walk_up: level %d: parent link %d outside the level's %d slots (pixel %d, from level %d)\n", k,
@@ -834,11 +800,7 @@ __global__ RT_LIGHT_BOUNDS void k_light(SceneHdr hdr, const double *__restrict__
 #define RT_LAST_WAVES_SPH 4 // the LAST launch of spheres-only scenes without the general pow (5: config 3 +0.5 %,
                             // config 5 +0.4 % per frame, profiles/r06k_ab_walk_unroll_last_waves.txt)
 #endif
-// The LAST launch shades a record's child before the record, once, with the child's colour (1), or the
-// record first with a +0.0 reflection and again with its shadow bits once the child is shaded (0).
-#ifndef RT_LAST_CHILD_FIRST
-#define RT_LAST_CHILD_FIRST 1
-#endif
+// The LAST launch shades a record's child before the record, once, with the child's colour.
 #if RT_FUSED_WAVES > 0
 #define RT_FUSED_BOUNDS                                                                                            \
     __launch_bounds__(BLOCK, LAST ? (SPH == 0 && GENPOW ? 2 : SPH == 0 || GENPOW ? 3 : RT_LAST_WAVES_SPH) :    \
@@ -869,7 +831,7 @@ __global__ RT_FUSED_BOUNDS void k_reflect_shade(SceneHdr hdr, const double *__re
     // shaded at once (the background reflection, its shadow tests) and its chain walked.
     const bool shade_here = k - 1 < 2 || (ILP && iw != 0) || deep_dense(nhits_prev - (k - 1));
     const bool walk_here = ILP && iw != 0 && shade_here;
-    // LAST kernels are launched for the deepest level only, with iw == 2 (rt_launch_spp, RT_RS), so there the
+    // LAST kernels are launched for the deepest level only, with iw == 2 (launch_wavefront), so there the
     // deepest-level path holds throughout: a compile-time constant, the other paths left out of them
     constexpr bool last_here = LAST;
     RT_LINK_CHECK(!LAST || (walk_here && iw == 2), "k_reflect_shade: LAST launched at level %d with iw %d\n", k, iw);
@@ -888,19 +850,12 @@ __global__ RT_FUSED_BOUNDS void k_reflect_shade(SceneHdr hdr, const double *__re
         // every pixel is written once per pass
         int cs = -1;
         ChildHit ch; // (last_here) the hit, not queued
-#ifndef RT_ABL_NO_REFLECT // timing ablation builds only (results wrong)
         cs = reflect_record<false, ILP, SPH, BVH>(SL, k, r, slot, act, h, N, q_k, cnt_k, nullptr, child_prev,
                                                   !last_here, LAST ? &ch : nullptr);
-#endif
         const bool child = cs >= 0;
         const int wslot = child ? cs : slot; // where the shading's result goes (one live register)
-#ifdef RT_ABL_NO_SHADE // timing ablation builds only (results wrong)
-        if (false) {
-#else
         if (shade_here) {
-#endif
             const double refl = obj_row<SPH>(SL, r.obj)[8];
-#if RT_LAST_CHILD_FIRST
             if constexpr (ILP && LAST) {
                 if (last_here) { // (wave-uniform)
                     // The deepest launch shades its hits where it finds them: the child first (as
@@ -929,37 +884,17 @@ __global__ RT_FUSED_BOUNDS void k_reflect_shade(SceneHdr hdr, const double *__re
                     return;
                 }
             }
-#endif
             unsigned bits = 0;
             const D3 F = shade<GENPOW, SPH>(SL, r.obj, D3{r.dx, r.dy, r.dz}, h, N, D3{0.0, 0.0, 0.0}, refl, act, &bits);
             if constexpr (ILP) {
-                if (walk_here) { // (wave-uniform)
-                    D3 c = F;
-                    const bool cl = last_here && act && child;
-                    const unsigned long long cm = __ballot(cl);
-                    if (cm) {
-                        // the child, as k_walk shades a record of the deepest level: the lanes without
-                        // one take the lead's operands (valid reads), then this record with its colour
-                        // and the shadow answers just found (its child's pbits, had it been queued)
-                        const int cl_lead = __builtin_ctzll(cm);
-                        const D3 hm = {h.x + ch.d.x * ch.t, h.y + ch.d.y * ch.t, h.z + ch.d.z * ch.t};
-                        const D3 hl = {readlane_d(hm.x, cl_lead), readlane_d(hm.y, cl_lead), readlane_d(hm.z, cl_lead)};
-                        const D3 dl = {readlane_d(ch.d.x, cl_lead), readlane_d(ch.d.y, cl_lead), readlane_d(ch.d.z, cl_lead)};
-                        const int il = __builtin_amdgcn_readlane(ch.id, cl_lead);
-                        const D3 hc = cl ? hm : hl, dc = cl ? ch.d : dl;
-                        const int idc = cl ? ch.id : il;
-                        const D3 cc = shade<GENPOW, SPH>(SL, idc, dc, hc, hit_normal<SPH>(SL, idc, hc), D3{0.0, 0.0, 0.0},
-                                                         obj_row<SPH>(SL, idc)[8], cl);
-                        const D3 cr = shade_bits<GENPOW, SPH>(SL, r.obj, D3{r.dx, r.dy, r.dz}, h, N, cc, refl, bits);
-                        if (cl) c = cr;
-                    }
+                if (walk_here) { // (wave-uniform; LAST kernels returned above)
                     // (the walk's inputs re-read from the kernel-argument segment instead, the
                     // header for level 0's rebuild too: SGPR spills 70 -> 44 (config 3), 48 -> 8
                     // (config 5), but config 5 +1.2 % per frame: each scalar reload's wait is also an
                     // LDS wait — profiles/r05z2_ab_inline_walk_variants.txt)
-                    walk_up<PREC, GENPOW, SPH>(SL, g, q0, lslots, k - 1, c, r.parent, (unsigned)r.pbits, r.pix,
-                                               act && (last_here || !child), out);
-                    if (act && child && !last_here) reinterpret_cast<unsigned *>(q_k + wslot)[15] = bits; // HitRec::pbits
+                    walk_up<PREC, GENPOW, SPH>(SL, g, q0, lslots, k - 1, F, r.parent, (unsigned)r.pbits, r.pix,
+                                               act && !child, out);
+                    if (act && child) reinterpret_cast<unsigned *>(q_k + wslot)[15] = bits; // HitRec::pbits
                     return;
                 }
             }
@@ -1020,13 +955,10 @@ __global__ RT_FUSED_BOUNDS void k_reflect_shade(SceneHdr hdr, const double *__re
 // and group g within it.  A chain walk from a deep terminal record is the longest work of the
 // launch, so those waves start first and the short level-1 walks fill in behind them (in level
 // order they started last and made the launch's tail).
-#ifndef RT_WALK_DEEP_FIRST
-#define RT_WALK_DEEP_FIRST 1
-#endif
 __device__ __forceinline__ bool level_group(const int *__restrict__ nhits, int lo, int hi, int u, int &j, int &g) {
     g = u;
     for (int i = lo; i < hi; ++i) {
-        j = RT_WALK_DEEP_FIRST ? hi - 1 - (i - lo) : i;
+        j = hi - 1 - (i - lo);
         const int ng = (nhits[j] + 63) >> 6;
         if (g < ng) return true;
         g -= ng;

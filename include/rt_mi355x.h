@@ -160,7 +160,7 @@ int rt_abi_version(void);
 const char *rt_strerror(int code);
 int rt_device_count(int *count);
 
-/* Diagnostic: the kernels' correctly rounded sqrt / division fast paths (rt_render.hip,
+/* Diagnostic: the kernels' correctly rounded sqrt / division fast paths (rt_math.inc,
  * sqrt_n / div_n: the device library's sequences without their range handling, used only
  * where every operand of the wave is in range) against the library, bit for bit, on n random
  * operands; *mismatches = the count of differing results (0 expected). */
@@ -177,7 +177,7 @@ int rt_selftest_math(int device, uint64_t n, uint64_t seed, uint64_t *mismatches
  *                        for kernels built without the general pow).
  *   RT_EVAL_POW_GENERAL  out[i] = pow_libm<true>(a[i], b[i]): any b
  *   RT_EVAL_SQRT         out[i] = sqrt_x<false>(a[i])
- *   RT_EVAL_DIV          out[i] = div_n(a[i], b[i]): no range handling, see rt_render.hip
+ *   RT_EVAL_DIV          out[i] = div_n(a[i], b[i]): no range handling, see rt_math.inc
  *   RT_EVAL_NORMALIZE3   a and out hold n vectors (3n values): out = normalize3(a, false)
  *   RT_EVAL_DIV_DIM      out[i] = div_dim(a[i], dim), 1 <= dim <= 2^20 (one scalar per call)
  *   RT_EVAL_IDIV_DIM     out[i] = idiv_dim((int)a[i], dim), a[i] an integer in [0, 2^31)

@@ -1,9 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel instruction counts of library variants (scripts/gpu_r06.sh TAG pmcv): the average of each
 PMC counter over every dispatch of a kernel instantiation, one table per variant, and each variant's
-difference from the first.  Counts do not depend on timing, so one short run per variant suffices;
-with the ablation builds (RT_ABL_NO_SHADE / RT_ABL_NO_REFLECT / RT_ABL_NO_OCC, results wrong) the
-differences attribute a kernel's executed instructions to its parts.
+difference from the first.  Counts do not depend on timing, so one short run per variant suffices.
 
     python3 scripts/pmc_variants.py DIR [KERNEL_SUBSTRING]   # DIR/<variant>/**/run_counter_collection.csv
 """

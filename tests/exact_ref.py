@@ -1,4 +1,4 @@
-"""Exact references for the kernels' arithmetic primitives (rt_render.hip: pow_libm, sqrt_x,
+"""Exact references for the kernels' arithmetic primitives (rt_math.inc: pow_libm, sqrt_x,
 div_n, normalize3, div_dim, idiv_dim), for tests/test_gpu_math_exact.py.  Not part of the product.
 
 * exact_pow / exact_sqrt / exact_div: Python integers only.  The operand's mantissa is taken to

@@ -1,6 +1,6 @@
 """tests/exact_ref.py checked on the CPU against independent arithmetic (mpmath at 200 bits,
 fractions.Fraction, the host's IEEE operations), glibc's pow measured against it, and the kernels'
-double-double powering (rt_render.hip: dd_sqr / dd_mul / pow_bin) restated with an exact fma to
+double-double powering (rt_math.inc: dd_sqr / dd_mul / pow_bin) restated with an exact fma to
 show which mistakes tests/test_gpu_math_exact.py catches."""
 import math
 import random

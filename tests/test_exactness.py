@@ -15,7 +15,7 @@ def _ref_sphere(B, disc):
 
 
 def _kernel_sphere(B, disc):
-    """sph_t / sph_t_wave (eraytracer_amd/csrc/rt_render.hip): the nearer root alone."""
+    """sph_t / sph_t_wave (eraytracer_amd/csrc/rt_math.inc): the nearer root alone."""
     t = (-B - np.sqrt(disc)) / 2
     return t >= 0, t
 

@@ -3,7 +3,7 @@ brute-force scans bit for bit.
 
 The production path skips objects that conservative filters prove a ray cannot hit: binary32
 wave beams (reflection and primary rays), per-light occluder masks split into direction cells,
-shadow cones and the binary32 sphere BVH of the deep reflection levels (rt_render.hip).  A filter
+shadow cones and the binary32 sphere BVH of the deep reflection levels (rt_cull.inc, rt_shade.inc).  A filter
 that dropped a true candidate would give a wrong hit on some rare pixel, so:
 
 * every pixel of the frames the bench renders (config 3: S64 4096^2 d5; S256 4096^2 d8, the

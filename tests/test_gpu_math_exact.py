@@ -1,4 +1,4 @@
-"""The kernels' arithmetic primitives (rt_render.hip: pow_libm / pow_bin, sqrt_x, div_n, normalize3,
+"""The kernels' arithmetic primitives (rt_math.inc: pow_libm / pow_bin, sqrt_x, div_n, normalize3,
 div_dim, idiv_dim) run on the GPU through rt_eval_math, one operand per work-item in array order
 (64 consecutive elements are one wave), against exact references (tests/exact_ref.py: Python
 integers rounded once; the host's IEEE sqrt and division), bit for bit.  Frames cannot judge
@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 STRUCTURED_N = (1, 2, 3, 4, 5, 7, 20, 21, 63, 64, 255, 256, 511, 512, 513, 768, 1000, 1023, 1024)
 EDGE_X = (0.0, 2.0 ** -1074, 2.0 ** -537, 0.5, 1.0 - 2.0 ** -53, 1.0, 1.0 + 2.0 ** -52, 1.0 + 2.0 ** -20)
 # Results below 2**-969 are within one unit in the last place (2**-1074 in the subnormal band) of the
-# correctly rounded value, not always equal to it (rt_render.hip, above dd_sqr; DESIGN.md section 3:
+# correctly rounded value, not always equal to it (rt_math.inc, above dd_sqr; DESIGN.md section 3:
 # the pairs' low parts are subnormal there).  Measured on MI355X, the same in all three layouts: 42
 # of 2,168 operands in [2**-1022, 2**-969) and 112 of 2,019 subnormal ones differ, each by 1.
 TINY_BAND_ULPS = 1
