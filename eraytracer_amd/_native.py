@@ -23,6 +23,11 @@ RT_OK, RT_DONE, RT_EBADARG, RT_ENODEV, RT_EHIP, RT_ENOMEM, RT_ETOOBIG = 0, 1, -1
 RT_ERANGE = -6
 RT_CAMERA, RT_POINT_LIGHT, RT_SPHERE, RT_TRIANGLE, RT_PLANE, RT_OTHER = range(6)
 RT_OUT_F64, RT_OUT_F32 = 0, 1
+RT_OUT_U8, RT_OUT_U16 = 2, 3  # integer frames (rt_render, rt_quantize)
+RT_MAX_INT_VALUE = 65535
+RT_STATS_PINNED, RT_STATS_CLAMPED = 1, 2
+# rt_quantize's kernel (csrc/rt_quant.hip): values per lane, per workgroup iteration, and the grid cap
+QUANT_V, QUANT_B, QUANT_MAX_BLOCKS = 8, 2048, 2048
 RT_ORDER_EXACT, RT_ORDER_FAST = 0, 1
 RT_MAX_SHARDS = 64
 RT_CFG_SIDE_STREAMS = 1
@@ -41,6 +46,7 @@ EXPORTS = (
     "rt_render", "rt_prepare", "rt_shard_rows", "rt_launch", "rt_launch_spp", "rt_unshard", "rt_configure", "rt_release",
     "rt_update_scene",
     "rt_ppm_bound", "rt_ppm_format", "rt_render_ppm_file",
+    "rt_quantize", "rt_render_rawppm_file",
     "rt_slab_header_bytes", "rt_slab_pack", "rt_slab_unpack", "rt_selftest_math",
     "rt_eval_math",
     "rt_host_alloc", "rt_host_free", "rt_reset_contexts", "rt_kernel_time", "rt_engine",
@@ -90,7 +96,7 @@ class RtOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("first_dev", ctypes.c_int32), ("ndev", ctypes.c_int32),
                 ("precision", ctypes.c_int32), ("order", ctypes.c_int32), ("row_block", ctypes.c_uint32),
                 ("out_levels", ctypes.c_void_p), ("spp", ctypes.c_uint32), ("nshards", ctypes.c_uint32),
-                ("seed", ctypes.c_uint64), ("flags", ctypes.c_uint32)]
+                ("seed", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("max_value", ctypes.c_uint32)]
 
 
 class RtStats(ctypes.Structure):
@@ -141,7 +147,9 @@ def lib() -> ctypes.CDLL:
     L.rt_ppm_bound.argtypes = [u32, u32, u32]
     L.rt_ppm_format.argtypes = [vp, i32, u32, u32, u32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), vp]
     L.rt_render_ppm_file.argtypes = [vp, u32, u32, u32, u32, vp, u32, ctypes.c_char_p, vp]
-    L.rt_unshard.argtypes = [vp, u32, u32, u32, u32, i32, vp, vp]
+    L.rt_quantize.argtypes = [vp, i32, ctypes.c_uint64, u32, i32, vp, vp, vp]
+    L.rt_render_rawppm_file.argtypes = [vp, u32, u32, u32, u32, vp, u32, ctypes.c_char_p, vp]
+    L.rt_unshard.argtypes =[vp, u32, u32, u32, u32, i32, vp, vp]
     L.rt_release.argtypes = [vp]
     L.rt_update_scene.argtypes = [vp, ctypes.POINTER(RtElem), u32]
     L.rt_configure.argtypes = [vp, i32, ctypes.c_int64]

@@ -10,7 +10,8 @@
 //    concurrent callers): streams, events, device buffers and work space are created once and
 //    grown on demand; the scene is recompiled only when its bytes change;
 //  * the frame is rendered in row bands, and each band's copy to the host runs on a second
-//    stream while the next band renders;
+//    stream while the next band renders; an integer frame's band is quantised (rt_quant.hip)
+//    behind its render on the render stream, and the copy moves the 1- or 2-byte samples;
 //  * a pinned destination (rt_host_alloc, or memory the caller registered with HIP) is written
 //    by DMA directly; a pageable one goes through a pinned staging ring of two bands, copied
 //    out by host threads while the next band's DMA is in flight.
@@ -84,6 +85,7 @@ struct rt_ctx {
     std::vector<unsigned char> key;              // bytes of the scene p was prepared from
     void *d_buf[3] = {};
     size_t d_cap[3] = {};
+    uint64_t *d_clamped = nullptr;               // integer frames: values stored as 0 (negative or NaN)
     void *h_stage = nullptr;
     size_t h_cap = 0;
 };
@@ -104,6 +106,7 @@ void destroy_ctx(rt_ctx *c) {
     if (c->p) rt_release(c->p);
     for (void *b : c->d_buf)
         if (b) (void)hipFree(b);
+    if (c->d_clamped) (void)hipFree(c->d_clamped);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     for (hipEvent_t e : c->band)
         if (e) (void)hipEventDestroy(e);
@@ -319,6 +322,22 @@ int rt_ctx_device_buffer(rt_ctx *c, int which, size_t bytes, void **out) {
     return RT_OK;
 }
 
+int rt_ctx_clamped(rt_ctx *c, uint64_t **out) {
+    if (!c->d_clamped) {
+        int prev = -1;
+        (void)hipGetDevice(&prev);
+        (void)hipSetDevice(c->device);
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&c->d_clamped), sizeof(uint64_t));
+        if (prev >= 0) (void)hipSetDevice(prev);
+        if (e != hipSuccess) {
+            c->d_clamped = nullptr;
+            return RT_ENOMEM;
+        }
+    }
+    *out = c->d_clamped;
+    return RT_OK;
+}
+
 int rt_ctx_host_buffer(rt_ctx *c, size_t bytes, void **out) {
     if (c->h_cap < bytes) {
         if (c->h_stage) {
@@ -493,7 +512,10 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height,
         if (o.ndev == 0) o.ndev = 1;
         if (opts->struct_size < offsetof(rt_opts, spp) + sizeof(o.spp) || o.spp == 0) o.spp = 1; // ABI 1 callers
     }
-    if (o.precision != RT_OUT_F64 && o.precision != RT_OUT_F32) return RT_EBADARG;
+    const bool integer = o.precision == RT_OUT_U8 || o.precision == RT_OUT_U16;
+    if (o.precision != RT_OUT_F64 && o.precision != RT_OUT_F32 && !integer) return RT_EBADARG;
+    if (o.max_value == 0) o.max_value = 255; // also a struct_size that ends before the field
+    if (integer && o.max_value > (o.precision == RT_OUT_U8 ? 255u : (uint32_t)RT_MAX_INT_VALUE)) return RT_ETOOBIG;
     if (o.order != RT_ORDER_EXACT && o.order != RT_ORDER_FAST) return RT_EBADARG;
     if (o.spp > RT_MAX_SPP) return RT_ETOOBIG;
     if (width > (1u << 20) || height > (1u << 20)) return RT_ETOOBIG;
@@ -512,8 +534,12 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height,
     if (ns > RT_MAX_SHARDS) return RT_ETOOBIG;
     const uint32_t nd = std::min<uint32_t>(ns, (uint32_t)o.ndev); // devices used; shard s on device s % nd
     const uint32_t slab = rt_shard_rows(height, rb, ns);
-    const size_t esz = o.precision == RT_OUT_F32 ? 4 : 8;
+    // an integer frame is rendered in binary64 (render_prec, rrow bytes per row) and quantised band
+    // by band into the integer slab; esz / rowbytes / slab_bytes describe what is copied to the host
+    const int render_prec = integer ? RT_OUT_F64 : o.precision;
+    const size_t esz = o.precision == RT_OUT_U8 ? 1 : o.precision == RT_OUT_U16 ? 2 : o.precision == RT_OUT_F32 ? 4 : 8;
     const uint32_t rowbytes = width * 3 * (uint32_t)esz;
+    const size_t rrow = (size_t)width * 3 * (render_prec == RT_OUT_F32 ? 4 : 8), rslab_bytes = (size_t)slab * rrow;
     const size_t frame_bytes = (size_t)height * rowbytes, slab_bytes = (size_t)slab * rowbytes;
     const bool pinned = is_pinned(out_rgb, frame_bytes);
     // bands: whole row blocks and whole tiles, about band_bytes() of output each, at most
@@ -529,8 +555,17 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height,
     int prev = -1;
     (void)hipGetDevice(&prev);
     std::vector<rt_ctx *> ctx(nd, nullptr);
-    std::vector<char *> d_out(nd, nullptr), stage(nd, nullptr);
+    std::vector<char *> d_out(nd, nullptr), stage(nd, nullptr); // d_out: the slabs the copies read
+    std::vector<char *> d_ren(nd, nullptr);                     // the slabs the kernels render into
     std::vector<uint8_t *> d_lv(nd, nullptr);
+    std::vector<uint64_t *> d_cl(nd, nullptr);
+    // image rows of shard s = its slab rows [0, valid): the rest of the slab is never rendered
+    auto valid_rows = [&](uint32_t s) -> uint32_t {
+        const uint64_t start = (uint64_t)s * rb, period = (uint64_t)ns * rb;
+        if (height <= start) return 0;
+        const uint64_t full = (height - start) / period, rem = (height - start) % period;
+        return (uint32_t)(full * rb + std::min<uint64_t>(rem, rb));
+    };
     int err = RT_OK;
     auto shards_of = [&](uint32_t d) { return (ns - d + nd - 1) / nd; }; // shards d, d + nd, ...
     for (uint32_t d = 0; d < nd && err == RT_OK; ++d) {
@@ -542,9 +577,17 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height,
         const uint32_t k = shards_of(d);
         // an allocation that fails while other contexts of the device sit idle on their memory is
         // retried once after those are trimmed (trim_idle)
-        err = rt_ctx_device_buffer(c, 0, k * slab_bytes, reinterpret_cast<void **>(&d_out[d]));
+        err = rt_ctx_device_buffer(c, 0, k * rslab_bytes, reinterpret_cast<void **>(&d_ren[d]));
         if (err == RT_ENOMEM && trim_idle(dev) > 0)
-            err = rt_ctx_device_buffer(c, 0, k * slab_bytes, reinterpret_cast<void **>(&d_out[d]));
+            err = rt_ctx_device_buffer(c, 0, k * rslab_bytes, reinterpret_cast<void **>(&d_ren[d]));
+        d_out[d] = d_ren[d];
+        if (err == RT_OK && integer) {
+            err = rt_ctx_device_buffer(c, 2, k * slab_bytes, reinterpret_cast<void **>(&d_out[d]));
+            if (err == RT_ENOMEM && trim_idle(dev) > 0)
+                err = rt_ctx_device_buffer(c, 2, k * slab_bytes, reinterpret_cast<void **>(&d_out[d]));
+            if (err == RT_OK) err = rt_ctx_clamped(c, &d_cl[d]);
+            if (err == RT_OK && hipMemsetAsync(d_cl[d], 0, sizeof(uint64_t), c->render) != hipSuccess) err = RT_EHIP;
+        }
         if (err == RT_OK && o.out_levels) {
             err = rt_ctx_device_buffer(c, 1, (size_t)k * slab * width, reinterpret_cast<void **>(&d_lv[d]));
             if (err == RT_ENOMEM && trim_idle(dev) > 0)
@@ -556,15 +599,21 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height,
         // every band's render on the render stream, its copy on the copy stream behind it
         for (uint32_t i = 0; i < k && err == RT_OK; ++i) {
             const uint32_t s = d + i * nd;
-            char *slab_out = d_out[d] + i * slab_bytes;
+            char *slab_out = d_out[d] + i * slab_bytes, *slab_ren = d_ren[d] + i * rslab_bytes;
             uint8_t *slab_lv = o.out_levels ? d_lv[d] + (size_t)i * slab * width : nullptr;
+            const uint32_t valid = valid_rows(s);
             for (uint32_t b = 0; b < nb && err == RT_OK; ++b) {
                 const uint32_t b0 = b * band, b1 = std::min(slab, b0 + band);
-                err = rt_launch_rows(c->p, width, height, depth, rb, s, ns, o.precision, o.order, o.spp, o.seed, b0,
-                                     b1, slab_out, slab_lv, c->render, (o.flags & RT_LEVELS_HIT) ? 1 : 0);
+                err = rt_launch_rows(c->p, width, height, depth, rb, s, ns, render_prec, o.order, o.spp, o.seed, b0,
+                                     b1, slab_ren, slab_lv, c->render, (o.flags & RT_LEVELS_HIT) ? 1 : 0);
                 if (err == RT_ENOMEM && trim_idle(dev) > 0) // (a failed grow launches nothing)
-                    err = rt_launch_rows(c->p, width, height, depth, rb, s, ns, o.precision, o.order, o.spp, o.seed,
-                                         b0, b1, slab_out, slab_lv, c->render, (o.flags & RT_LEVELS_HIT) ? 1 : 0);
+                    err = rt_launch_rows(c->p, width, height, depth, rb, s, ns, render_prec, o.order, o.spp, o.seed,
+                                         b0, b1, slab_ren, slab_lv, c->render, (o.flags & RT_LEVELS_HIT) ? 1 : 0);
+                // integer frame: the band's image rows quantised behind its render, before its event
+                if (err == RT_OK && integer && b0 < std::min(b1, valid))
+                    err = rt_quantize(slab_ren + (size_t)b0 * rrow, RT_OUT_F64,
+                                      (uint64_t)(std::min(b1, valid) - b0) * width * 3, o.max_value, o.precision,
+                                      slab_out + (size_t)b0 * rowbytes, d_cl[d], c->render);
                 if (err == RT_OK && hipEventRecord(c->band[i * nb + b], c->render) != hipSuccess) err = RT_EHIP;
                 if (err == RT_OK && pinned) {
                     hipStream_t cs = ((i * nb + b) % copy_streams()) ? c->copy2 : c->copy;
@@ -627,6 +676,7 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height,
                          rb, d + i * nd, ns, reinterpret_cast<char *>(o.out_levels));
     }
     double kms = 0;
+    uint64_t clamped = 0;
     for (uint32_t d = 0; d < nd; ++d) {
         rt_ctx *c = ctx[d];
         if (!c) continue;
@@ -636,6 +686,11 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height,
         if (hipStreamSynchronize(c->copy2) != hipSuccess && err == RT_OK) err = RT_EHIP;
         float ms = 0;
         if (err == RT_OK && hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess && ms > kms) kms = ms;
+        if (err == RT_OK && d_cl[d]) {
+            uint64_t cnt = 0;
+            if (hipMemcpy(&cnt, d_cl[d], sizeof cnt, hipMemcpyDeviceToHost) != hipSuccess) err = RT_EHIP;
+            clamped += cnt;
+        }
         rt_ctx_release(c);
     }
     if (prev >= 0) (void)hipSetDevice(prev);
@@ -644,7 +699,7 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height,
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
         stats->pixels = (uint64_t)width * height;
         stats->ndev = (int32_t)nd;
-        stats->flags = pinned ? 1 : 0;
+        stats->flags = (pinned ? RT_STATS_PINNED : 0) | (clamped ? RT_STATS_CLAMPED : 0);
     }
     return err;
 }

@@ -38,6 +38,10 @@ void rt_ctx_release(rt_ctx *c);
 rt_prepared *rt_ctx_prepared(rt_ctx *c);
 hipStream_t rt_ctx_stream(rt_ctx *c);
 // Device buffer `which` (0..2) of at least `bytes`, kept (and grown) with the context.
+// 0: the float frame, 1: the levels, 2: the P3 text or the integer frame.
 int rt_ctx_device_buffer(rt_ctx *c, int which, size_t bytes, void **out);
+// The context's counter of values an integer frame stored as 0 (rt_quantize's d_clamped): 8 bytes
+// of device memory, created on first use; the caller zeroes it on its stream.
+int rt_ctx_clamped(rt_ctx *c, uint64_t **out);
 // Pinned host staging buffer of at least `bytes`, kept with the context.
 int rt_ctx_host_buffer(rt_ctx *c, size_t bytes, void **out);

@@ -1,0 +1,295 @@
+// rt_quant.hip — integer frames on the GPU: the value rule of write_pixels_to_ppm/5
+// (raytracer.erl:667-685) without the text, and the binary P6 file made from it.
+//
+// Every channel becomes min(trunc(C*MaxValue), MaxValue) in binary64, as quantise() in
+// rt_ppm.hip computes it; an unsigned sample cannot hold what P3 prints as a negative number, so
+// a result below 0 (C*MaxValue <= -1) or a NaN is stored as 0 and counted.  -0.0 and products in
+// (-1, 0) truncate to 0 and are not counted.
+//
+// k_quant is bound by HBM bandwidth (24 B read, 3 B written per pixel of a binary64 frame to
+// 8 bits).  The frame is a flat array: a lane takes QUANT_V = 8 consecutive values per iteration
+// with 16-byte loads (four for binary64, two for binary32) and writes them with one store of
+// 8 bytes (8-bit samples) or 16 bytes (16-bit samples), so a wave's stores are contiguous; a
+// workgroup covers QUANT_B = 2048 values per iteration, the grid is capped at QUANT_MAX_BLOCKS
+// workgroups and strides over the rest.  Up to 15 leading values (until the output is 16-byte
+// aligned) and up to 7 trailing ones are done one by one by the first workgroup; when the input
+// is not 16-byte aligned behind that head, the body loads element by element (same bytes).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../../include/rt_mi355x.h"
+#include "rt_internal.h"
+
+namespace {
+
+constexpr int QUANT_BLOCK = 256;                 // work-items per workgroup
+constexpr int QUANT_V = 8;                       // values per lane per iteration
+constexpr int QUANT_B = QUANT_BLOCK * QUANT_V;   // values per workgroup per iteration
+constexpr int QUANT_MAX_BLOCKS = 2048;           // grid cap (256 CUs x 8 workgroups)
+static_assert(QUANT_V == 8 && QUANT_B == 2048, "load8 / store8 take 8 values; _native.py mirrors these as QUANT_*");
+
+#define QCHK(x)                                                                                                    \
+    do {                                                                                                           \
+        hipError_t e_ = (x);                                                                                       \
+        if (e_ != hipSuccess) {                                                                                    \
+            std::fprintf(stderr, "rt_mi355x: %s failed: %s\n", #x, hipGetErrorString(e_));                        \
+            return RT_EHIP;                                                                                        \
+        }                                                                                                          \
+    } while (0)
+
+// min(trunc(c * maxv), maxv), or 0 with *bad set when that is negative or not a number
+__device__ inline unsigned quant1(double c, double maxv, unsigned maxi, bool *bad) {
+    const double x = c * maxv;
+    if (!(x > -1.0)) {       // trunc(x) <= -1, or NaN
+        *bad = true;
+        return 0u;
+    }
+    if (x >= maxv) return maxi; // also +inf
+    return (unsigned)(int)x;    // (-1, maxv): the conversion truncates toward zero
+}
+
+template <typename TIN, bool VEC>
+__device__ inline void load8(const TIN *p, double v[QUANT_V]);
+
+template <>
+__device__ inline void load8<double, true>(const double *p, double v[QUANT_V]) {
+    const double2 *q = reinterpret_cast<const double2 *>(p);
+#pragma unroll
+    for (int k = 0; k < QUANT_V / 2; ++k) {
+        const double2 a = q[k];
+        v[2 * k] = a.x;
+        v[2 * k + 1] = a.y;
+    }
+}
+template <>
+__device__ inline void load8<float, true>(const float *p, double v[QUANT_V]) {
+    const float4 *q = reinterpret_cast<const float4 *>(p);
+#pragma unroll
+    for (int k = 0; k < QUANT_V / 4; ++k) {
+        const float4 a = q[k];
+        v[4 * k] = (double)a.x;
+        v[4 * k + 1] = (double)a.y;
+        v[4 * k + 2] = (double)a.z;
+        v[4 * k + 3] = (double)a.w;
+    }
+}
+template <>
+__device__ inline void load8<double, false>(const double *p, double v[QUANT_V]) {
+#pragma unroll
+    for (int k = 0; k < QUANT_V; ++k) v[k] = p[k];
+}
+template <>
+__device__ inline void load8<float, false>(const float *p, double v[QUANT_V]) {
+#pragma unroll
+    for (int k = 0; k < QUANT_V; ++k) v[k] = (double)p[k];
+}
+
+// p is 16-byte aligned (the host's head)
+__device__ inline void store8(uint8_t *p, const unsigned q[QUANT_V]) {
+    uint2 w;
+    w.x = q[0] | q[1] << 8 | q[2] << 16 | q[3] << 24;
+    w.y = q[4] | q[5] << 8 | q[6] << 16 | q[7] << 24;
+    *reinterpret_cast<uint2 *>(p) = w;
+}
+__device__ inline void store8(uint16_t *p, const unsigned q[QUANT_V]) {
+    uint4 w;
+    w.x = q[0] | q[1] << 16;
+    w.y = q[2] | q[3] << 16;
+    w.z = q[4] | q[5] << 16;
+    w.w = q[6] | q[7] << 16;
+    *reinterpret_cast<uint4 *>(p) = w;
+}
+
+// in/out: the whole array of n values; [head, head + nvec*QUANT_V) is the vector body, out + head
+// 16-byte aligned (and in + head too when VEC).  *clamped += the values stored as 0 because they
+// were negative or NaN: one atomic per wave that has any.
+template <typename TIN, typename TOUT, bool VEC>
+__global__ __launch_bounds__(QUANT_BLOCK) void k_quant(const TIN *__restrict__ in, TOUT *__restrict__ out, uint64_t n,
+                                                       uint32_t head, uint64_t nvec, double maxv, unsigned maxi,
+                                                       unsigned long long *__restrict__ clamped) {
+    unsigned nbad = 0; // wave-uniform: every count below comes from a ballot
+    const TIN *bin = in + head;
+    TOUT *bout = out + head;
+    // wave-uniform trip count, so that the ballots see the whole wave
+    const uint64_t stride = (uint64_t)gridDim.x * QUANT_BLOCK;
+    const uint64_t wave0 = (uint64_t)blockIdx.x * QUANT_BLOCK + (threadIdx.x & ~63u);
+    for (uint64_t base = wave0; base < nvec; base += stride) {
+        const uint64_t c = base + (threadIdx.x & 63u);
+        unsigned badmask = 0;
+        if (c < nvec) {
+            double v[QUANT_V];
+            unsigned q[QUANT_V];
+            load8<TIN, VEC>(bin + c * QUANT_V, v);
+#pragma unroll
+            for (int k = 0; k < QUANT_V; ++k) {
+                bool bad = false;
+                q[k] = quant1(v[k], maxv, maxi, &bad);
+                badmask |= (bad ? 1u : 0u) << k;
+            }
+            store8(bout + c * QUANT_V, q);
+        }
+        if (__ballot(badmask != 0)) { // rare: count value by value
+#pragma unroll
+            for (int k = 0; k < QUANT_V; ++k) nbad += (unsigned)__popcll(__ballot((badmask >> k) & 1u));
+        }
+    }
+    if (blockIdx.x == 0) { // the scalar head and tail: fewer than 16 + 8 values
+        const uint64_t tail0 = (uint64_t)head + nvec * QUANT_V;
+        const uint64_t t = threadIdx.x;
+        const uint64_t i = t < head ? t : tail0 + (t - head); // threads [head, head + tail) take the tail
+        bool bad = false;
+        if (i < n) out[i] = (TOUT)quant1((double)in[i], maxv, maxi, &bad);
+        nbad += (unsigned)__popcll(__ballot(bad));
+    }
+    if (nbad && clamped && (threadIdx.x & 63u) == 0) atomicAdd(clamped, (unsigned long long)nbad);
+}
+
+template <typename TIN, typename TOUT>
+void launch_quant(const void *in, void *out, uint64_t n, uint32_t head, bool vec, double maxv, unsigned maxi,
+                  unsigned long long *clamped, hipStream_t st) {
+    const uint64_t nvec = (n - head) / QUANT_V;
+    const uint64_t want = (nvec + QUANT_BLOCK - 1) / QUANT_BLOCK;
+    const unsigned grid = (unsigned)(want < 1 ? 1 : want > QUANT_MAX_BLOCKS ? QUANT_MAX_BLOCKS : want);
+    if (vec)
+        hipLaunchKernelGGL((k_quant<TIN, TOUT, true>), dim3(grid), dim3(QUANT_BLOCK), 0, st,
+                           static_cast<const TIN *>(in), static_cast<TOUT *>(out), n, head, nvec, maxv, maxi, clamped);
+    else
+        hipLaunchKernelGGL((k_quant<TIN, TOUT, false>), dim3(grid), dim3(QUANT_BLOCK), 0, st,
+                           static_cast<const TIN *>(in), static_cast<TOUT *>(out), n, head, nvec, maxv, maxi, clamped);
+}
+
+void p6_header(char h[64], uint32_t W, uint32_t H, uint32_t maxv) { std::snprintf(h, 64, "P6\n%u %u\n%u\n", W, H, maxv); }
+
+// the samples of a native-endian integer frame, 16-bit ones most significant byte first
+int write_p6(const char *path, uint32_t W, uint32_t H, uint32_t maxv, void *samples) {
+    const size_t nval = (size_t)W * H * 3;
+    if (maxv > 255) {
+        uint16_t *s = static_cast<uint16_t *>(samples);
+        for (size_t i = 0; i < nval; ++i) {
+            const unsigned char b[2] = {(unsigned char)(s[i] >> 8), (unsigned char)(s[i] & 0xFF)};
+            std::memcpy(&s[i], b, 2);
+        }
+    }
+    FILE *f = std::fopen(path, "wb");
+    if (!f) return RT_EBADARG;
+    char h[64];
+    p6_header(h, W, H, maxv);
+    const size_t bytes = nval * (maxv > 255 ? 2 : 1);
+    int rc = RT_OK;
+    if (std::fwrite(h, 1, std::strlen(h), f) != std::strlen(h) || std::fwrite(samples, 1, bytes, f) != bytes)
+        rc = RT_EBADARG;
+    if (std::fclose(f) != 0) rc = RT_EBADARG;
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_quantize(const void *d_rgb, int precision, uint64_t n_values, uint32_t max_value, int out_format, void *d_out,
+                uint64_t *d_clamped, void *stream) {
+    if (!d_rgb || !d_out) return RT_EBADARG;
+    if (precision != RT_OUT_F64 && precision != RT_OUT_F32) return RT_EBADARG;
+    if (out_format != RT_OUT_U8 && out_format != RT_OUT_U16) return RT_EBADARG;
+    if (max_value == 0) return RT_EBADARG;
+    if (max_value > (out_format == RT_OUT_U8 ? 255u : (uint32_t)RT_MAX_INT_VALUE)) return RT_ETOOBIG;
+    const size_t isz = precision == RT_OUT_F64 ? 8 : 4, osz = out_format == RT_OUT_U8 ? 1 : 2;
+    if ((uintptr_t)d_rgb % isz || (uintptr_t)d_out % osz || (uintptr_t)d_clamped % 8) return RT_EBADARG;
+    if (n_values == 0) return RT_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // the head: values before the output's first 16-byte boundary
+    uint64_t head = ((16 - (uintptr_t)d_out % 16) % 16) / osz;
+    if (head > n_values) head = n_values;
+    const bool vec = ((uintptr_t)d_rgb + head * isz) % 16 == 0;
+    const double maxv = (double)max_value;
+    unsigned long long *cl = reinterpret_cast<unsigned long long *>(d_clamped);
+    if (precision == RT_OUT_F64 && out_format == RT_OUT_U8)
+        launch_quant<double, uint8_t>(d_rgb, d_out, n_values, (uint32_t)head, vec, maxv, max_value, cl, st);
+    else if (precision == RT_OUT_F64)
+        launch_quant<double, uint16_t>(d_rgb, d_out, n_values, (uint32_t)head, vec, maxv, max_value, cl, st);
+    else if (out_format == RT_OUT_U8)
+        launch_quant<float, uint8_t>(d_rgb, d_out, n_values, (uint32_t)head, vec, maxv, max_value, cl, st);
+    else
+        launch_quant<float, uint16_t>(d_rgb, d_out, n_values, (uint32_t)head, vec, maxv, max_value, cl, st);
+    QCHK(hipGetLastError());
+    return RT_OK;
+}
+
+int rt_render_rawppm_file(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height, uint32_t depth,
+                          const rt_opts *opts, uint32_t max_value, const char *path, rt_stats *stats) {
+    if (!path) return RT_EBADARG;
+    if (width == 0 && height == 0) return RT_DONE;
+    if (width == 0 || height == 0) return RT_EBADARG;
+    if (max_value == 0) return RT_EBADARG;
+    if (max_value > RT_MAX_INT_VALUE) return RT_ETOOBIG;
+    rt_opts o;
+    std::memset(&o, 0, sizeof o);
+    o.ndev = 1;
+    o.row_block = 16;
+    o.spp = 1;
+    if (opts && opts->struct_size) std::memcpy(&o, opts, opts->struct_size < sizeof o ? opts->struct_size : sizeof o);
+    if (o.spp == 0) o.spp = 1;
+    if (o.row_block == 0) o.row_block = 16;
+    if (o.ndev == 0) o.ndev = 1;
+    const int fmt = max_value > 255 ? RT_OUT_U16 : RT_OUT_U8;
+    const size_t osz = fmt == RT_OUT_U16 ? 2 : 1;
+    const size_t nval = (size_t)width * height * 3;
+    o.struct_size = sizeof o;
+    o.precision = fmt;
+    o.max_value = max_value;
+    o.out_levels = nullptr;
+    int rc = RT_OK;
+    if (o.ndev != 1) { // several devices: rt_render assembles the integer frame on the host
+        std::vector<unsigned char> img(nval * osz);
+        rt_stats st;
+        std::memset(&st, 0, sizeof st);
+        rc = rt_render(scene, n, width, height, depth, &o, img.data(), &st);
+        if (rc != RT_OK) return rc;
+        if (stats) *stats = st;
+        if (st.flags & RT_STATS_CLAMPED) return RT_ERANGE; // P3 would print a negative number
+        return write_p6(path, width, height, max_value, img.data());
+    }
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || o.first_dev < 0 || o.first_dev >= nd) return RT_ENODEV;
+    rt_ctx *ctx = nullptr;
+    rc = rt_ctx_acquire(o.first_dev, scene, n, &ctx);
+    if (rc != RT_OK) return rc;
+    (void)hipSetDevice(o.first_dev);
+    void *d_rgb = nullptr, *d_int = nullptr, *h_int = nullptr;
+    uint64_t *d_clamped = nullptr;
+    uint64_t clamped = 0;
+    hipStream_t st = rt_ctx_stream(ctx);
+    do {
+        if ((rc = rt_ctx_device_buffer(ctx, 0, nval * sizeof(double), &d_rgb)) != RT_OK) break;
+        if ((rc = rt_ctx_device_buffer(ctx, 2, nval * osz, &d_int)) != RT_OK) break;
+        if ((rc = rt_ctx_clamped(ctx, &d_clamped)) != RT_OK) break;
+        if ((rc = rt_ctx_host_buffer(ctx, nval * osz, &h_int)) != RT_OK) break;
+        if (hipMemsetAsync(d_clamped, 0, sizeof clamped, st) != hipSuccess) { rc = RT_EHIP; break; }
+        rc = rt_launch_spp(rt_ctx_prepared(ctx), width, height, depth, o.row_block, 0, 1, RT_OUT_F64, o.order, o.spp,
+                           o.seed, d_rgb, nullptr, st);
+        if (rc != RT_OK) break;
+        if ((rc = rt_quantize(d_rgb, RT_OUT_F64, nval, max_value, fmt, d_int, d_clamped, st)) != RT_OK) break;
+        // the samples and the counter to pinned memory by DMA; the file is written from there
+        if (hipMemcpyAsync(h_int, d_int, nval * osz, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(&clamped, d_clamped, sizeof clamped, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) { rc = RT_EHIP; break; }
+        if (clamped) { rc = RT_ERANGE; break; } // before the path is opened: no file
+        rc = write_p6(path, width, height, max_value, h_int);
+    } while (0);
+    (void)hipStreamSynchronize(st);
+    rt_ctx_release(ctx);
+    if (prev >= 0) (void)hipSetDevice(prev);
+    if (stats && (rc == RT_OK || rc == RT_ERANGE)) {
+        stats->pixels = (uint64_t)width * height;
+        stats->ndev = 1;
+    }
+    return rc;
+}
+
+} // extern "C"

@@ -52,12 +52,20 @@ def _depth_ok(depth):
         raise ValueError(f"badarg: Recursion_depth {depth} does not fit the library's 32-bit depth")
 
 
+def _max_value_ok(max_value):
+    if isinstance(max_value, bool) or not isinstance(max_value, int) or not 0 < max_value < 1 << 32:
+        raise ValueError(f"badarg: MaxValue must be an integer in [1, 2^32), got {max_value!r}")
+
+
 def render(width: int, height: int, scene=None, depth: int = 5, *, precision: str = "f64",
            order: str = "exact", ndev: int = 1, first_dev: int = 0, row_block: int = 16,
            levels: bool = False, stats: dict | None = None, spp: int = 1, seed: int = 0, out=None,
-           nshards: int = 0):
+           nshards: int = 0, max_value: int = 255):
     """Render through ``rt_render`` and return a ``(height, width, 3)`` array (float64 or
     float32), plus the per-pixel levels array if ``levels``.  ``'done'`` for 0x0.
+    ``precision="u8"`` / ``"u16"``: an integer frame (uint8 / uint16) quantised on the GPU,
+    every channel ``min(trunc(C*max_value), max_value)`` — the integers write_pixels_to_ppm/5
+    prints; a negative or NaN channel is stored as 0 and ``stats["clamped"]`` is then true.
     ``out``: an existing C-contiguous array of that shape and dtype to render into (e.g.
     ``_native.pinned_empty``: pinned memory is written by DMA directly).  ``nshards``: row
     shards of the distributed split (default one per device; shard s on device s % ndev).
@@ -73,8 +81,9 @@ def render(width: int, height: int, scene=None, depth: int = 5, *, precision: st
         scene = default_scene()
     elems = N.marshal(scene)
     L = N.lib()
-    prec = {"f64": N.RT_OUT_F64, "f32": N.RT_OUT_F32}[precision]
-    dt = np.float64 if prec == N.RT_OUT_F64 else np.float32
+    prec, dt = {"f64": (N.RT_OUT_F64, np.float64), "f32": (N.RT_OUT_F32, np.float32),
+                "u8": (N.RT_OUT_U8, np.uint8), "u16": (N.RT_OUT_U16, np.uint16)}[precision]
+    _max_value_ok(max_value)
     if out is None:
         out = np.empty((height, width, 3), dtype=dt)
     elif out.shape != (height, width, 3) or out.dtype != dt or not out.flags.c_contiguous:
@@ -83,7 +92,7 @@ def render(width: int, height: int, scene=None, depth: int = 5, *, precision: st
     opts = N.RtOpts(ctypes.sizeof(N.RtOpts), first_dev, ndev, prec,
                     {"exact": N.RT_ORDER_EXACT, "fast": N.RT_ORDER_FAST}[order], row_block,
                     lv.ctypes.data if levels else None, spp, nshards, seed,
-                    N.RT_LEVELS_HIT if levels == "hit" else 0)
+                    N.RT_LEVELS_HIT if levels == "hit" else 0, max_value)
     st = N.RtStats()
     rc = L.rt_render(elems, len(elems), width, height, depth, ctypes.byref(opts), out.ctypes.data, ctypes.byref(st))
     if rc == N.RT_DONE:
@@ -91,7 +100,7 @@ def render(width: int, height: int, scene=None, depth: int = 5, *, precision: st
     N.check(rc, "rt_render")
     if stats is not None:
         stats.update(kernel_ms=st.kernel_ms, total_ms=st.total_ms, pixels=st.pixels, ndev=st.ndev,
-                     pinned=bool(st.flags & 1))
+                     pinned=bool(st.flags & N.RT_STATS_PINNED), clamped=bool(st.flags & N.RT_STATS_CLAMPED))
     return (out, lv) if levels else out
 
 
@@ -186,6 +195,53 @@ def write_pixels_to_ppm(Width, Height, MaxValue, Pixels, Filename):
             f.write("".join(parts))
 
 
+def write_pixels_to_p6(Width, Height, MaxValue, Pixels, Filename):
+    """The binary sibling of :func:`write_pixels_to_ppm` (not in the reference): the header
+    ``P6\\nW H\\nMaxValue\\n`` followed by the same integers ``min(trunc(C*MaxValue), MaxValue)``
+    as samples, 1 byte each for MaxValue <= 255, else 2 bytes each, most significant byte first.
+    Accepts the pixel list or a (H, W, 3) array; a value P3 would print as negative cannot be a
+    sample and raises ValueError (so does a NaN), before the file is opened.  The host mirror of
+    rt_render_rawppm_file."""
+    if isinstance(MaxValue, bool) or not isinstance(MaxValue, int) or not 0 < MaxValue <= N.RT_MAX_INT_VALUE:
+        raise ValueError(f"badarg: MaxValue must be an integer in [1, {N.RT_MAX_INT_VALUE}], got {MaxValue!r}")
+    if isinstance(Pixels, np.ndarray):
+        c = Pixels.astype(np.float64).reshape(-1)
+    else:
+        c = np.array([[float(r), float(g), float(b)] for _key, (r, g, b) in Pixels], dtype=np.float64).reshape(-1)
+    if c.size != Width * Height * 3:
+        raise ValueError(f"badarg: {c.size} channels for a {Width}x{Height} frame")
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = np.trunc(c * float(MaxValue))
+        bad = ~(t >= 0)  # negative (not -0.0) or NaN
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"channel {k % 3} of pixel {k // 3} is {c[k]!r}: no unsigned sample holds it")
+    q = np.minimum(t, float(MaxValue)).astype(">u2" if MaxValue > 255 else np.uint8)
+    with open(Filename, "wb") as f:
+        f.write(f"P6\n{Width} {Height}\n{MaxValue}\n".encode("ascii"))
+        f.write(q.tobytes())
+
+
+def quantize_gpu(img, max_value: int = 255, dtype=np.uint8):
+    """An array of binary64 or binary32 channels quantised on the GPU (rt_quantize) to ``dtype``
+    (uint8 or uint16): ``(array of img's shape, clamped_count)``, the count being the values
+    stored as 0 because they were negative or NaN.  The sibling of :func:`ppm_text_gpu`."""
+    import torch
+    L = N.lib()
+    dt = np.dtype(dtype)
+    fmt = {np.dtype(np.uint8): N.RT_OUT_U8, np.dtype(np.uint16): N.RT_OUT_U16}[dt]
+    prec = N.RT_OUT_F64 if img.dtype == np.float64 else N.RT_OUT_F32
+    src = np.ascontiguousarray(img, dtype=np.float64 if prec == N.RT_OUT_F64 else np.float32)
+    d = torch.from_numpy(src).cuda()
+    out = torch.empty(max(src.size, 1) * dt.itemsize, dtype=torch.uint8, device="cuda")
+    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    N.check(L.rt_quantize(d.data_ptr(), prec, src.size, max_value, fmt, out.data_ptr(), cnt.data_ptr(), st),
+            "rt_quantize")
+    torch.cuda.synchronize()
+    return out[: src.size * dt.itemsize].cpu().numpy().view(dt).reshape(src.shape), int(cnt.item())
+
+
 def raytrace(Width=4, Height=3, Filename="/tmp/traced.ppm", Recursion_depth=5, Function=None):
     """raytrace/1,5 (raytracer.erl:721-733): render scene() with Function, write the PPM.
     The GPU strategy goes through rt_render_ppm_file (the P3 text is produced on the GPU,
@@ -199,18 +255,24 @@ def raytrace(Width=4, Height=3, Filename="/tmp/traced.ppm", Recursion_depth=5, F
 
 
 def render_ppm_file(width: int, height: int, scene, depth: int, filename: str, *, max_value: int = 255,
-                    ndev: int = 1, first_dev: int = 0, spp: int = 1, seed: int = 0):
-    """Render and write the P3 file natively (rt_render_ppm_file): raytrace/5 + write_pixels_to_ppm/5."""
+                    ndev: int = 1, first_dev: int = 0, spp: int = 1, seed: int = 0, binary: bool = False):
+    """Render and write the P3 file natively (rt_render_ppm_file): raytrace/5 + write_pixels_to_ppm/5.
+    ``binary=True``: the P6 file of the same integers (rt_render_rawppm_file; see
+    :func:`write_pixels_to_p6`); a frame with a negative value raises RtError (RT_ERANGE) and
+    no file is written."""
     if not _sizes_ok(width, height):
         return DONE
     _depth_ok(depth)
+    if binary:
+        _max_value_ok(max_value)
     elems = N.marshal(scene)
     opts = N.RtOpts(ctypes.sizeof(N.RtOpts), first_dev, ndev, N.RT_OUT_F64, N.RT_ORDER_EXACT, 16, None, spp, 0, seed)
-    rc = N.lib().rt_render_ppm_file(elems, len(elems), width, height, depth, ctypes.byref(opts), max_value,
-                                    str(filename).encode(), None)
+    what = "rt_render_rawppm_file" if binary else "rt_render_ppm_file"
+    rc = getattr(N.lib(), what)(elems, len(elems), width, height, depth, ctypes.byref(opts), max_value,
+                                str(filename).encode(), None)
     if rc == N.RT_DONE:
         return DONE
-    N.check(rc, "rt_render_ppm_file")
+    N.check(rc, what)
     return "ok"
 
 

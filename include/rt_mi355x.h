@@ -100,6 +100,12 @@ typedef struct rt_elem {
 /* ---- options / statistics ---------------------------------------------------- */
 #define RT_OUT_F64 0   /* out_rgb is double[H][W][3] (the reference's values, exact) */
 #define RT_OUT_F32 1   /* out_rgb is float[H][W][3]  (the "float3 framebuffer") */
+/* Integer frames: every channel is min(trunc(C*max_value), max_value) of the binary64 value C,
+ * the rule of write_pixels_to_ppm/5 (raytracer.erl:667-685), so the samples are the integers the
+ * P3 file prints.  An unsigned sample cannot hold a negative one: see rt_quantize. */
+#define RT_OUT_U8  2   /* uint8_t [H][W][3], max_value 1..255   */
+#define RT_OUT_U16 3   /* uint16_t[H][W][3], native endian, max_value 1..65535 */
+#define RT_MAX_INT_VALUE 65535
 
 #define RT_ORDER_EXACT 0 /* reflection added once per light, reference fold order (bit-identical colour sums) */
 #define RT_ORDER_FAST 1  /* forward-only reassociated accumulation (|delta| ~ 1e-15, same hit decisions) */
@@ -112,7 +118,7 @@ typedef struct rt_opts {
                              per process) makes rt_render see N devices that are all first_dev; one
                              call then holds N of the device's 4 contexts, so the hook supports one
                              rt_render caller at a time (concurrent callers with N >= 3 can deadlock) */
-    int32_t precision;    /* RT_OUT_F64 (default) or RT_OUT_F32 */
+    int32_t precision;    /* RT_OUT_F64 (default), RT_OUT_F32, or an integer frame: RT_OUT_U8, RT_OUT_U16 */
     int32_t order;        /* RT_ORDER_EXACT (default) or RT_ORDER_FAST */
     uint32_t row_block;   /* multi-device interleave granularity in rows (default 16) */
     uint8_t *out_levels;  /* optional host W*H bytes: reflection-chain levels that hit, per pixel */
@@ -127,6 +133,9 @@ typedef struct rt_opts {
                              object (depth > 0), 0 elsewhere, instead of the chain's level count —
                              all a host needs for the reference's integer {0,0,0} pixels, and it keeps
                              the fused shading kernels that a full level count turns off */
+    /* appended after ABI 4's flags (additive: RT_ABI_VERSION stays 5) */
+    uint32_t max_value;   /* RT_OUT_U8 / RT_OUT_U16: the samples' MaxValue; 0, or a struct_size that
+                             ends before this field, selects 255 */
 } rt_opts;
 #define RT_LEVELS_HIT 1
 
@@ -148,12 +157,17 @@ typedef struct rt_opts {
 #define RT_MAX_SPP 4096
 
 typedef struct rt_stats {
-    double kernel_ms;   /* device time of the render kernels (max over devices) */
+    double kernel_ms;   /* device time of the render kernels, and of an integer frame's quantise
+                           passes between them (max over devices) */
     double total_ms;    /* wall time of the whole call, boundary to boundary */
     uint64_t pixels;    /* W*H */
     int32_t ndev;       /* devices actually used */
-    int32_t flags;      /* bit 0: out_rgb was pinned host memory (written by DMA directly) */
+    int32_t flags;      /* bit 0: out_rgb was pinned host memory (written by DMA directly);
+                           bit 1 (RT_STATS_CLAMPED): an integer frame stored at least one channel as
+                           0 because it was negative or NaN (the call still returns RT_OK) */
 } rt_stats;
+#define RT_STATS_PINNED 1
+#define RT_STATS_CLAMPED 2
 
 /* ---- library / device ------------------------------------------------------------ */
 int rt_abi_version(void);
@@ -218,7 +232,12 @@ int rt_scene_canon(rt_elem *scene, uint32_t n_elems);
  * colours, flags, lists; spp > 1 adds the binary64 sums, 24 B per pixel) plus its output
  * buffers (the frame, 201 MB at 4096^2 f32); it is kept while the context is idle.  An
  * allocation that fails while other contexts of the device are idle is retried once after their
- * memory is freed (a busy context's is never touched); rt_reset_contexts frees it all. */
+ * memory is freed (a busy context's is never touched); rt_reset_contexts frees it all.
+ * Integer frames (precision RT_OUT_U8 / RT_OUT_U16, opts->max_value): every row band is rendered
+ * in binary64 and quantised on the GPU (rt_quantize) before its copy, so out_rgb receives 3 or
+ * 6 bytes per pixel instead of 24; the context keeps the binary64 frame and the integer one.
+ * Every other option works as for float frames.  RT_ETOOBIG for a max_value above the format's
+ * limit; a channel that was negative or NaN is stored as 0 and sets RT_STATS_CLAMPED. */
 int rt_render(const rt_elem *scene, uint32_t n_elems, uint32_t width, uint32_t height,
               uint32_t depth, const rt_opts *opts, void *out_rgb, rt_stats *stats);
 
@@ -342,6 +361,37 @@ int rt_ppm_format(const void *d_rgb, int precision, uint32_t width, uint32_t hei
 int rt_render_ppm_file(const rt_elem *scene, uint32_t n_elems, uint32_t width, uint32_t height,
                        uint32_t depth, const rt_opts *opts, uint32_t max_value, const char *path,
                        rt_stats *stats);
+
+/* ---- integer frames and the binary P6 file ------------------------------------------------
+ * rt_quantize: a device array of n_values channels (precision as rt_launch writes it; a frame
+ *   is taken as a flat array, no pixel structure is needed) to 8- or 16-bit samples in d_out,
+ *   asynchronously on `stream`; it neither synchronises nor allocates.
+ *     out[i] = min(trunc((double)in[i] * (double)max_value), max_value)     (binary64)
+ *   the rule of the P3 writer above, so +inf gives max_value.  What an unsigned sample cannot
+ *   hold — a result below 0, or a NaN — is stored as 0, and *d_clamped (optional, device memory,
+ *   zeroed by the caller) is increased by the number of such values; -0.0 and values in
+ *   (-1/max_value, 0) truncate to 0 and are not counted.
+ *   Alignment: d_rgb aligned to its element (8 bytes for RT_OUT_F64, 4 for RT_OUT_F32), d_out to
+ *   its own (1 or 2 bytes), d_clamped to 8; anything else is RT_EBADARG.  Any such pair works: the
+ *   values before d_out's first 16-byte boundary and the last n % 8 are converted one by one, the
+ *   rest with 16-byte loads when d_rgb is 16-byte aligned at that boundary (element loads
+ *   otherwise: slower, same bytes) and 8- or 16-byte stores.
+ *   RT_EBADARG for a null d_rgb or d_out, a bad precision or out_format, or max_value 0;
+ *   RT_ETOOBIG for a max_value above the format's limit; n_values 0 launches nothing.  The
+ *   arguments are checked before any HIP call.
+ * rt_render_rawppm_file: rt_render_ppm_file for the binary ("raw", magic P6) format:
+ *   "P6\nW H\nMaxValue\n" followed by the samples of the P3 file, 1 byte each for
+ *   max_value <= 255, else 2 bytes each, most significant byte first.  A frame with a value P3
+ *   would print as negative cannot be written: RT_ERANGE, and no file is created.  RT_ETOOBIG for
+ *   max_value > RT_MAX_INT_VALUE, RT_EBADARG for 0; a width or height of 0 as in
+ *   rt_render_ppm_file.  (Entry-point names hold no digits: the export list is matched against
+ *   this header by letters and underscores alone.) */
+int rt_quantize(const void *d_rgb, int precision /* RT_OUT_F64|RT_OUT_F32 */, uint64_t n_values,
+                uint32_t max_value, int out_format /* RT_OUT_U8|RT_OUT_U16 */, void *d_out,
+                uint64_t *d_clamped /* optional, device */, void *stream);
+int rt_render_rawppm_file(const rt_elem *scene, uint32_t n_elems, uint32_t width, uint32_t height,
+                          uint32_t depth, const rt_opts *opts, uint32_t max_value,
+                          const char *path, rt_stats *stats);
 
 #ifdef __cplusplus
 }
