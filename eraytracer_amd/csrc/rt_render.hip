@@ -82,7 +82,9 @@ struct rt_prepared {
     // grow, rt_trim and rt_release go through this one list
     enum Work {
         W_QUEUE,  // HitRec[slab pixels * depth]
-        W_COLBUF, // double: colours of levels 1 .. depth-1, COL_W doubles per slot
+        // double: colours of levels 1 .. depth-1, COL_W doubles per slot; inline-walk frames write none,
+        // and those of LDS-staged scenes keep the per-light terms of levels 1 .. depth-2 here
+        W_COLBUF,
         W_CHILD,  // uint8_t per level and slot: the record's reflection hit something
         W_LIT,    // unsigned per level and slot: shadow answers of lights 0..31 (k_light)
         W_SAMPLE, // double: supersampling, one sample's slab and the running sum
@@ -626,11 +628,37 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
     // colours of levels 1 .. depth-1, COL_W doubles per slot (level 0 goes straight to the
     // frame), and per level the has-a-child flags
     const size_t col_doubles = slots * COL_W * (size_t)std::max(1, nlev - 1);
-    if (rc == RT_OK) rc = grow(p, rt_prepared::W_COLBUF, col_doubles * sizeof(double));
+    const bool overlap = lit_overlap(p) && D > 1 && p->hdr.n_light > 0;
+    const int nrefl = (p->hdr.n_light > 0 && D > 1) ? D - 1 : 0;
+    // no side streams (frames in flight): each level's shading fused into the next reflection
+    // pass (k_reflect_shade)
+    const bool fuse = !overlap && !levels && nrefl > 0;
+    // Inline walks (k_reflect_shade's iw, levels >= 1): every level is shaded by the launch that
+    // reflects it; the chain of a shaded record without a child is walked by that launch, and the
+    // deepest level's hits are shaded and walked by the launch that finds them (not queued) — what
+    // k_walk did, minus its launch, the deepest level's k_items, the terminal records' colour entries
+    // and their re-reads.  Needs the shadow answers in the records (<= 32 lights) and two reflection
+    // levels or more (level 1's kernel, the dominant one, is left as is).  For S64 the dense
+    // arrangement this implies measured the same as the sparse one (profiles/r05aa_ab_memset_dense.txt).
+    const bool iw = fuse && p->hdr.n_light <= 32 && nrefl >= 2;
+    // spheres only, culling on: every shadow target has occluder masks (lit_by<1>); their
+    // per-lane-gathered tables staged in each workgroup's LDS when they fit (SPH = 2)
+    const bool sph_only = p->hdr.n_tri == 0 && p->hdr.n_pl == 0 && p->hdr.cull_ok && p->hdr.occ_ok;
+    const bool staged = sph_only && p->hdr.l_bytes > 0;
+    // ... and for LDS-staged scenes of up to TERM_MAX_LIGHTS lights those walks fold the child's
+    // colour into per-light terms stored at the first shading instead of shading again (walk_fold):
+    // one entry per slot of the queued levels 1 .. nrefl-1.  An inline-walk launch writes no colour
+    // entries, so the entries take the colour buffer, grown to the larger of its two uses.  (Staged
+    // scenes only: S256 depth 8 with its tables in L2 and dense deep levels measured 2.7 % slower per
+    // frame with the entries than reshading, profiles/terms_ab_c3.txt; only the SPH = 2 kernels
+    // compile the entries in.)
+    const bool fold = iw && staged && p->hdr.n_light <= TERM_MAX_LIGHTS;
+    const size_t term_bytes =
+        fold ? slots * (size_t)(nrefl - 1) * term_stride(p->hdr.n_light) * sizeof(double2) : 0;
+    if (rc == RT_OK) rc = grow(p, rt_prepared::W_COLBUF, std::max(col_doubles * sizeof(double), term_bytes));
     if (rc == RT_OK) rc = grow(p, rt_prepared::W_CHILD, slots * nlev);
     if (rc == RT_OK) rc = grow(p, rt_prepared::W_LIT, slots * nlev * sizeof(unsigned));
     if (rc == RT_OK) rc = grow(p, rt_prepared::W_COUNTS, max_tiles * nlev * sizeof(int));
-    const bool overlap = lit_overlap(p) && D > 1 && p->hdr.n_light > 0;
     // dense work lists: 64 per-level record counts, then per level the slots of its records in tile order
     const size_t list0 = level_counts(nlev);
     const size_t items_ints = list0 + slots * nlev;
@@ -671,12 +699,7 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
     unsigned *const d_lit = p->buf<unsigned>(rt_prepared::W_LIT);
     int *const d_counts = p->buf<int>(rt_prepared::W_COUNTS);
     int *const d_items = p->buf<int>(rt_prepared::W_ITEMS);
-    const int nrefl = (p->hdr.n_light > 0 && D > 1) ? D - 1 : 0;
     const int nshade = D > 0 ? 1 + nrefl : 0;
-    // spheres only, culling on: every shadow target has occluder masks (lit_by<1>); their
-    // per-lane-gathered tables staged in each workgroup's LDS when they fit (SPH = 2)
-    const bool sph_only = p->hdr.n_tri == 0 && p->hdr.n_pl == 0 && p->hdr.cull_ok && p->hdr.occ_ok;
-    const bool staged = sph_only && p->hdr.l_bytes > 0;
     const size_t lds = staged ? (size_t)p->hdr.l_bytes : 0; // the SPH = 2 kernels' dynamic LDS; 0 for SPH < 2
     // Reflection kernels of levels that traverse the sphere BVH: after the staged tables in LDS,
     // the BVH nodes and sphere rows (when they fit BVH_LDS_MAX) and every lane's stack.
@@ -695,17 +718,7 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
     // (LDS-staged scenes keep the candidate walks: their tables and the BVH would not fit together)
     auto bvh_at = [&](int k) { return !staged && rhdr.bvh_ok && k >= rhdr.bvh_level; };
     auto lds_r = [&](int k) { return bvh_at(k) ? lds_bvh : lds; };
-    // no side streams (frames in flight): each level's shading fused into the next reflection
-    // pass (k_reflect_shade)
-    const bool fuse = !overlap && !levels && nrefl > 0;
-    // Inline walks (k_reflect_shade's iw, levels >= 1): every level is shaded by the launch that
-    // reflects it; the chain of a shaded record without a child is walked by that launch, and the
-    // deepest level's hits are shaded and walked by the launch that finds them (not queued) — what
-    // k_walk did, minus its launch, the deepest level's k_items, the terminal records' colour entries
-    // and their re-reads.  Needs the shadow answers in the records (<= 32 lights) and two reflection
-    // levels or more (level 1's kernel, the dominant one, is left as is).  For S64 the dense
-    // arrangement this implies measured the same as the sparse one (profiles/r05aa_ab_memset_dense.txt).
-    const bool iw = fuse && p->hdr.n_light <= 32 && nrefl >= 2;
+    double2 *const d_terms = fold ? reinterpret_cast<double2 *>(d_colbuf) : nullptr;
     for (int row0 = row_begin; row0 < row_end; row0 += pass_rows) {
         const int rows = std::min(pass_rows, row_end - row0);
         const int ntiles = tiles_x * ((rows + TILE - 1) / TILE);
@@ -784,7 +797,7 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
                             (k_reflect_shade<PREC, GENPOW, SPH, decltype(ilp_c)::value, BVH, decltype(last_c)::value>),
                             dim3(k == 1 ? sblocks1 : BVH ? sblocksb : sblocks), dim3(BLOCK), lds_r(k), st, rhdr, p->d_tab,
                             p->d_itab, k, o, qk(k - 1), ik(k - 1), nitems + (k - 1), qk(k), ck(k), iw ? nullptr : chk(k - 1),
-                            colk(k - 1), g, iw && k >= 2 ? (k == nrefl ? 2 : 1) : 0);
+                            colk(k - 1), g, iw && k >= 2 ? (k == nrefl ? 2 : 1) : 0, d_terms);
                     };
                     auto rs_ilp = [&](auto bvh_c) {
                         with_bool(last, [&](auto last_c) { rs(std::true_type{}, bvh_c, last_c); });

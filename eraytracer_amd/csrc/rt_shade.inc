@@ -383,9 +383,18 @@ __device__ __forceinline__ bool lit_by(const Scene &S, int light, const Target &
 // OPQ (col a live value, not the background's constant): col is made opaque inside the light loop,
 // so col * refl is formed per light as written instead of being hoisted out of the loop into three
 // more live doubles (the fused kernel spilled them).
+// terms, tslot, tstore (optional; k_reflect_shade's first shading of a record whose reflection was
+// queued, tstore on the lanes that have such a child): light i's {dd, sp} — everything of its term
+// that does not depend on the reflected colour — goes to entry tslot (the child's slot) of `terms`,
+// for the chain walk to fold the child's colour in without shading the record again (walk_fold,
+// rt_wave.inc).
+constexpr int TERM_MAX_LIGHTS = 8; // more lights: no entries, the walk reshades (walk_up)
+// double2 per entry: 64-byte entries up to 4 lights, 128-byte ones up to TERM_MAX_LIGHTS
+__host__ __device__ constexpr int term_stride(int n_light) { return n_light <= 4 ? 4 : 8; }
 template <bool GENPOW, int SPH = 0, bool NB = false, bool OPQ = false>
 __device__ __forceinline__ D3 shade(const Scene &S, int id, const D3 &d, const D3 &hit, const D3 &N, const D3 &col,
-                                    double refl, bool active, unsigned *bits = nullptr) {
+                                    double refl, bool active, unsigned *bits = nullptr, double2 *terms = nullptr,
+                                    int tslot = 0, bool tstore = false) {
     const SceneHdr &h = S.h;
     if (__ballot(active) == 0) return D3{0.0, 0.0, 0.0}; // no hit to shade in this wave
     const Target T = make_target<SPH>(S, id, active);
@@ -416,6 +425,7 @@ __device__ __forceinline__ D3 shade(const Scene &S, int id, const D3 &d, const D
         // specular_term/7 (:285-297)
         const D3 hn = normalize3(D3{ln.x + -d.x, ln.y + -d.y, ln.z + -d.z});
         const double sp = shin * pow_libm<GENPOW>(max0(dot3(hn, N)), spow, active);
+        if (terms && active && tstore) terms[(size_t)tslot * term_stride(h.n_light) + i] = double2{dd, sp};
         const D3 spec = {Sc.x * sp, Sc.y * sp, Sc.z * sp};
         const D3 con = {diff.x + spec.x, diff.y + spec.y, diff.z + spec.z};
         // A lane whose light term Lc (x) con is exactly zero gets the same bits for lit = 0 and

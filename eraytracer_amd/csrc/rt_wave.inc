@@ -700,6 +700,82 @@ __device__ __forceinline__ void walk_up(const Scene &S, const PassGeom &g, const
     if (on) put_pixel<PREC>(out, g, (size_t)pix, c);
 }
 
+// walk_up from stored per-light terms (LDS-staged scenes of at most TERM_MAX_LIGHTS lights): when k_reflect_shade first
+// shaded an ancestor it left every light's {dd, sp} in the entry of the ancestor's queued child
+// (shade's terms; entries of level k + 1 at terms + k * level_slots * stride, indexed by the child's
+// slot as pbits is).  Nothing else in a light's term depends on the child's colour, so a step only
+// folds the colour in — from diff on, shade_bits's operations on the same operands in the same order,
+// so the same bits — with no hit normal, normalize3 or pow, and no ray rebuilt at level 0.  A step
+// reads the entry at the walk's current slot (the record at level lv is in `slot`) and the
+// ancestor's last 16 bytes {pix, obj, parent, pbits} — at level 0 its Rec0.  Lanes off the walk
+// follow the lead lane's slots, so every read is of a valid entry.
+template <int PREC, int SPH>
+__device__ __forceinline__ void walk_fold(const Scene &S, const PassGeom &g, const HitRec *__restrict__ q,
+                                          size_t level_slots, int lv, D3 c, int slot, int parent, unsigned pb, int pix,
+                                          bool on, void *__restrict__ out, const double2 *__restrict__ terms) {
+    const unsigned long long m = __ballot(on);
+    if (m == 0) return;
+    const int lead = __builtin_ctzll(m);
+    const SceneHdr &h = S.h;
+    const int stride = term_stride(h.n_light);
+    for (int k = lv - 1; k >= 0; --k) { // (wave-uniform: one level per step)
+        RT_LINK_CHECK(!on || (unsigned)parent < (unsigned)level_slots,
+                      "walk_fold: level %d: parent link %d outside the level's %d slots (pixel %d, from level %d)\n", k,
+                      parent, (int)level_slots, pix, lv);
+        RT_LINK_CHECK(!on || (unsigned)slot < (unsigned)level_slots,
+                      "walk_fold: level %d: slot %d outside the level's %d slots (pixel %d, from level %d)\n", k + 1,
+                      slot, (int)level_slots, pix, lv);
+        const int lp = __builtin_amdgcn_readlane(parent, lead), lcs = __builtin_amdgcn_readlane(slot, lead);
+        int ps = on ? parent : lp, cs = on ? slot : lcs;
+        ps = (unsigned)ps < (unsigned)level_slots ? ps : 0; // kept inside the level (see RT_LINK_CHECK)
+        cs = (unsigned)cs < (unsigned)level_slots ? cs : 0;
+        const double2 *e = terms + ((size_t)k * level_slots + cs) * stride;
+        int4 t; // the ancestor's {pix, obj, parent, pbits}
+        if (k == 0) {
+            const Rec0 r0 = reinterpret_cast<const Rec0 *>(q)[ps];
+            t = int4{r0.pix, r0.obj, -1, 0};
+        } else {
+            t = *reinterpret_cast<const int4 *>(&q[(size_t)k * level_slots + ps].pix);
+        }
+        RT_LINK_CHECK(!on || t.x == pix, "walk_fold: level %d slot %d: parent of pixel %d holds pixel %d\n", k, ps, pix,
+                      t.x);
+        const double *mr = obj_row<SPH>(S, t.y);
+        const double refl = mr[8];
+        D3 F = {0.0, 0.0, 0.0};
+        // four lights' terms per load (an entry holds a multiple of four): one memory wait per step
+        // of the walk's dependent chain, beside the record's, instead of one per light
+        for (int i0 = 0; i0 < h.n_light; i0 += 4) {
+            const double2 e0 = e[i0], e1 = e[i0 + 1], e2 = e[i0 + 2], e3 = e[i0 + 3];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int i = i0 + j;
+                if (i >= h.n_light) break;
+                const double *L = S.tab + h.o_light + i * LIGHT_W;
+                const D3 Lc = {L[0], L[1], L[2]}, Sc = {L[6], L[7], L[8]};
+                const double2 m34 = *reinterpret_cast<const double2 *>(mr + 4);
+                const D3 mc = {mr[3], m34.x, m34.y};
+                const double2 ds = j == 0 ? e0 : j == 1 ? e1 : j == 2 ? e2 : e3;
+                const double dd = ds.x, sp = ds.y;
+                const D3 diff = {mc.x * dd, mc.y * dd, mc.z * dd};
+                const D3 spec = {Sc.x * sp, Sc.y * sp, Sc.z * sp};
+                const D3 con = {diff.x + spec.x, diff.y + spec.y, diff.z + spec.z};
+                const D3 lc = {Lc.x * con.x, Lc.y * con.y, Lc.z * con.z};
+                const double lit = ((pb >> i) & 1u) ? 1.0 : 0.0;
+                D3 cc = c; // opaque: c * refl formed per light, not hoisted (see shade)
+                asm volatile("" : "+v"(cc.x), "+v"(cc.y), "+v"(cc.z));
+                F.x = F.x + (cc.x * refl + lc.x * lit);
+                F.y = F.y + (cc.y * refl + lc.y * lit);
+                F.z = F.z + (cc.z * refl + lc.z * lit);
+            }
+        }
+        c = F;
+        slot = ps;
+        parent = t.z;
+        pb = (unsigned)t.w;
+    }
+    if (on) put_pixel<PREC>(out, g, (size_t)pix, c);
+}
+
 // Where a level-k colour goes: the frame at level 0, the level's colour array otherwise — one
 // 32-byte entry per slot (COL_W doubles): the colour and, in the last word, the record's
 // (parent, pbits) word copied from `link` (the record's own), so the chain walk starts a terminal
@@ -819,15 +895,19 @@ __global__ RT_FUSED_BOUNDS void k_reflect_shade(SceneHdr hdr, const double *__re
                                                 const HitRec *__restrict__ q_prev, const int *__restrict__ idx_prev,
                                                 const int *__restrict__ nhits_prev, HitRec *__restrict__ q_k,
                                                 int *__restrict__ cnt_k, uint8_t *__restrict__ child_prev,
-                                                double *__restrict__ col_prev, PassGeom g, int iw) {
+                                                double *__restrict__ col_prev, PassGeom g, int iw,
+                                                double2 *__restrict__ terms_staged) {
     const Scene S{hdr, tab, itab};
     if (no_records_for_block(nhits_prev)) return; // before staging: sparse levels' idle blocks
     stage_tables<SPH>(S);
     if (BVH) stage_bvh(S);
+    // Per-light terms (shade's terms, walk_fold): launch_wavefront passes them for LDS-staged scenes
+    // only, so the other instantiations are compiled without them (their registers as before)
+    double2 *const terms = SPH == 2 ? terms_staged : nullptr;
     // Inline walks (iw != 0; ILP kernels, levels k - 1 >= 1, at most 32 lights): every level is shaded
     // by the launch that reflects it (the dense arrangement, whatever level 2's population), and a
-    // shaded record without a child is final: its chain is walked here (walk_up) — no colour entry,
-    // no k_walk.  iw == 2 marks the deepest level's launch: its hits are not queued at all — each is
+    // shaded record without a child is final: its chain is walked here (walk_up, or walk_fold from the
+    // stored terms) — no colour entry, no k_walk.  iw == 2 marks the deepest level's launch: its hits are not queued at all — each is
     // shaded at once (the background reflection, its shadow tests) and its chain walked.
     const bool shade_here = k - 1 < 2 || (ILP && iw != 0) || deep_dense(nhits_prev - (k - 1));
     const bool walk_here = ILP && iw != 0 && shade_here;
@@ -880,20 +960,32 @@ __global__ RT_FUSED_BOUNDS void k_reflect_shade(SceneHdr hdr, const double *__re
                         if (cl) cc = c1;
                     }
                     const D3 c = shade<GENPOW, SPH, false, true>(SL, r.obj, D3{r.dx, r.dy, r.dz}, h, N, cc, refl, act);
-                    walk_up<PREC, GENPOW, SPH>(SL, g, q0, lslots, k - 1, c, r.parent, (unsigned)r.pbits, r.pix, act, out);
+                    if (terms) // (wave-uniform)
+                        walk_fold<PREC, SPH>(SL, g, q0, lslots, k - 1, c, slot, r.parent, (unsigned)r.pbits, r.pix, act, out,
+                                             terms);
+                    else
+                        walk_up<PREC, GENPOW, SPH>(SL, g, q0, lslots, k - 1, c, r.parent, (unsigned)r.pbits, r.pix, act, out);
                     return;
                 }
             }
             unsigned bits = 0;
-            const D3 F = shade<GENPOW, SPH>(SL, r.obj, D3{r.dx, r.dy, r.dz}, h, N, D3{0.0, 0.0, 0.0}, refl, act, &bits);
+            // (terms: a record with a queued child leaves its per-light terms in the child's entry of level k;
+            // wslot serves both the entry and the walk below — the child's slot or the record's own)
+            const D3 F = shade<GENPOW, SPH>(SL, r.obj, D3{r.dx, r.dy, r.dz}, h, N, D3{0.0, 0.0, 0.0}, refl, act, &bits,
+                                            terms ? terms + (size_t)(k - 1) * lslots * term_stride(SL.h.n_light) : nullptr,
+                                            wslot, child);
             if constexpr (ILP) {
                 if (walk_here) { // (wave-uniform; LAST kernels returned above)
                     // (the walk's inputs re-read from the kernel-argument segment instead, the
                     // header for level 0's rebuild too: SGPR spills 70 -> 44 (config 3), 48 -> 8
                     // (config 5), but config 5 +1.2 % per frame: each scalar reload's wait is also an
                     // LDS wait — profiles/r05z2_ab_inline_walk_variants.txt)
-                    walk_up<PREC, GENPOW, SPH>(SL, g, q0, lslots, k - 1, F, r.parent, (unsigned)r.pbits, r.pix,
-                                               act && !child, out);
+                    if (terms) // (wave-uniform)
+                        walk_fold<PREC, SPH>(SL, g, q0, lslots, k - 1, F, wslot, r.parent, (unsigned)r.pbits, r.pix,
+                                             act && !child, out, terms);
+                    else
+                        walk_up<PREC, GENPOW, SPH>(SL, g, q0, lslots, k - 1, F, r.parent, (unsigned)r.pbits, r.pix,
+                                                   act && !child, out);
                     if (act && child) reinterpret_cast<unsigned *>(q_k + wslot)[15] = bits; // HitRec::pbits
                     return;
                 }
