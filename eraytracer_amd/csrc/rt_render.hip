@@ -1091,8 +1091,10 @@ static int scatter_slab(const char *slab, uint32_t rowbytes, uint32_t H, uint32_
 int rt_unshard(const void *d_slabs, uint32_t width, uint32_t height, uint32_t row_block, uint32_t nshards,
                int precision, void *d_image, void *stream) {
     if (!d_slabs || !d_image || width == 0 || height == 0 || row_block == 0 || nshards == 0) return RT_EBADARG;
-    if (precision != RT_OUT_F64 && precision != RT_OUT_F32) return RT_EBADARG;
-    uint32_t rowbytes = width * 3 * (precision == RT_OUT_F64 ? 8 : 4);
+    if (precision != RT_OUT_F64 && precision != RT_OUT_F32 && precision != RT_OUT_U8 && precision != RT_OUT_U16)
+        return RT_EBADARG;
+    uint32_t esz = precision == RT_OUT_F64 ? 8 : precision == RT_OUT_F32 ? 4 : precision == RT_OUT_U16 ? 2 : 1;
+    uint32_t rowbytes = width * 3 * esz;
     uint64_t slab_bytes = (uint64_t)rt_shard_rows(height, row_block, nshards) * rowbytes;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     for (uint32_t s = 0; s < nshards; s++) {

@@ -21,6 +21,11 @@
 // rt_unshard: one workgroup per image row and 256 columns (the row's shard and slab row are
 // wave-uniform), one thread per pixel finds its mask bit and reads its value, so the full
 // frame is written once.
+//
+// Integer slabs (RT_OUT_U8 / RT_OUT_U16: a binary64 slab quantised by rt_quantize where it was
+// rendered) take the same header; their values are 3 or 6 bytes per non-zero pixel, and a pixel
+// is zero iff its three samples are.  Mask and compaction are the same kernels on 1- and 2-byte
+// elements; the decode of an aligned frame is k_unpack_int (48 bytes of an image row per thread).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -277,10 +282,171 @@ __global__ __launch_bounds__(SLAB_BLOCK) void k_unpack4(ShardPtrs sp, uint64_t m
     }
 }
 
+// ---- integer frames: 48 bytes of an image row per thread ------------------------------------
+// A thread of k_unpack_int decodes INT_BYTES / PB consecutive pixels (PB = 3 or 6 bytes per pixel:
+// 16 pixels of u8, 8 of u16).  Its non-zero pixels are consecutive in the values array, so they are
+// one run of at most 48 bytes: read with aligned dword loads whatever the values pointer's
+// alignment, brought to byte 0 with a funnel shift, and expanded by the mask bits in registers.
+constexpr int INT_BYTES = 48, INT_DW = INT_BYTES / 4;
+
+// the dword at byte `sh` (0..3) of the pair hi:lo
+__host__ __device__ inline uint32_t funnel(uint32_t hi, uint32_t lo, unsigned sh) {
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * sh));
+}
+
+// w: a run of packed PB-byte pixels from byte 0 (what follows the popc(bits) pixels of the run is
+// never used); o: the 48 / PB pixels of the mask `bits` in place, zero where a bit is clear.  Pixel
+// k takes the run's first pixel and, if its bit is set, the run moves down by one pixel; only the
+// dwords that the pixels still to come can reach are moved.  Every index is a compile-time
+// constant, so w and o stay in registers.
+template <int PB>
+__host__ __device__ inline void expand_run(uint32_t (&w)[INT_DW], unsigned bits, uint32_t (&o)[INT_DW]) {
+    constexpr int G = INT_BYTES / PB;
+#pragma unroll
+    for (int i = 0; i < INT_DW; ++i) o[i] = 0;
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+        const bool take = (bits >> k) & 1u;
+        const int d = k * PB / 4, s = k * PB % 4 * 8; // pixel k starts at bit s of o[d]
+        if constexpr (PB == 3) {
+            const uint32_t v = take ? (w[0] & 0xFFFFFFu) : 0u;
+            o[d] |= v << s;
+            if (s > 8) o[d + 1] |= v >> (32 - s);
+        } else {
+            const uint32_t lo = take ? w[0] : 0u, hi = take ? (w[1] & 0xFFFFu) : 0u;
+            if (s == 0) {
+                o[d] |= lo;
+                o[d + 1] |= hi;
+            } else { // s == 16
+                o[d] |= lo << 16;
+                o[d + 1] |= (lo >> 16) | (hi << 16);
+            }
+        }
+        const int need = ((G - 1 - k) * PB + 3) / 4; // dwords the remaining pixels occupy
+#pragma unroll
+        for (int i = 0; i < need; ++i) {
+            uint32_t moved;
+            if constexpr (PB == 3)
+                moved = funnel(i + 1 < INT_DW ? w[i + 1] : 0u, w[i], 3);
+            else
+                moved = funnel(i + 2 < INT_DW ? w[i + 2] : 0u, i + 1 < INT_DW ? w[i + 1] : 0u, 2);
+            w[i] = take ? moved : w[i];
+        }
+    }
+}
+
+// One workgroup per (image row g, 256 threads' pixels: 4096 columns of u8, 2048 of u16).  The width
+// is a multiple of the thread's pixel count G, so p is one and the thread's mask bits sit in one
+// word (G divides 64).  The 48 bytes go through LDS to the frame as in k_unpack4: lane i of a store
+// at 16 i bytes of the workgroup's contiguous stretch, non-temporal.
+template <typename T>
+__global__ __launch_bounds__(SLAB_BLOCK) void k_unpack_int(ShardPtrs sp, uint64_t mask_at, uint64_t px, uint32_t W,
+                                                            uint32_t ncol, uint32_t rb, uint32_t ns,
+                                                            T *__restrict__ image) {
+    constexpr int PB = 3 * (int)sizeof(T), G = INT_BYTES / PB, Q = INT_BYTES / 16;
+    __shared__ uint4 s_out[SLAB_BLOCK * Q];
+    const uint32_t g = blockIdx.x / ncol, c = blockIdx.x - g * ncol;
+    const uint32_t x0 = c * SLAB_BLOCK * G, x = x0 + threadIdx.x * G;
+    const uint32_t nact = (W - x0 < SLAB_BLOCK * G ? W - x0 : SLAB_BLOCK * G) / G;
+    if (x < W) {
+        const uint32_t blk = g / rb, s = blk % ns;
+        const uint64_t lr = (uint64_t)(blk / ns) * rb + (g - blk * rb);
+        const uint64_t p = lr * W + x; // a multiple of G (W is)
+        const unsigned char *h = sp.hdr[s];
+        const uint32_t *off = reinterpret_cast<const uint32_t *>(h + HDR_OFFS);
+        const uint64_t *mask = reinterpret_cast<const uint64_t *>(h + mask_at);
+        const unsigned bits = (unsigned)(mask[p / 64] >> (p % 64)) & ((1u << G) - 1u);
+        uint32_t o[INT_DW];
+#pragma unroll
+        for (int i = 0; i < INT_DW; ++i) o[i] = 0;
+        if (bits) {
+            const uint64_t r = rank_of(off, mask, p);
+            const uint32_t n = (uint32_t)__popc(bits);
+            if (r + n <= px) { // (a consistent header never ranks past the slab)
+                // the run's bytes [a, a + n PB) lie inside the values buffer; every dword loaded is
+                // an aligned one that holds at least one of them
+                const uintptr_t a = reinterpret_cast<uintptr_t>(sp.vals[s]) + r * PB;
+                const unsigned sh = (unsigned)(a & 3);
+                const uint32_t *src = reinterpret_cast<const uint32_t *>(a - sh);
+                const uint32_t ndw = (sh + n * PB + 3) / 4; // <= INT_DW + 1
+                uint32_t cdw[INT_DW + 1];
+#pragma unroll
+                for (int i = 0; i <= INT_DW; ++i) cdw[i] = (uint32_t)i < ndw ? src[i] : 0u;
+                uint32_t w[INT_DW];
+#pragma unroll
+                for (int i = 0; i < INT_DW; ++i) w[i] = funnel(cdw[i + 1], cdw[i], sh);
+                expand_run<PB>(w, bits, o);
+            }
+        }
+        uint4 *so = s_out + threadIdx.x * Q;
+#pragma unroll
+        for (int k = 0; k < Q; ++k) so[k] = make_uint4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
+    }
+    __syncthreads();
+    uint4 *out = reinterpret_cast<uint4 *>(image + ((uint64_t)g * W + x0) * 3);
+    const uint32_t n16 = nact * Q;
+#pragma unroll
+    for (int k = 0; k < Q; ++k) {
+        const uint32_t i = k * SLAB_BLOCK + threadIdx.x;
+        if (i < n16) {
+            typedef unsigned v4u __attribute__((ext_vector_type(4)));
+            const uint4 v = s_out[i];
+            __builtin_nontemporal_store(v4u{v.x, v.y, v.z, v.w}, reinterpret_cast<v4u *>(out + i));
+        }
+    }
+}
+
 bool args_ok(uint32_t width, uint32_t height, uint32_t row_block, uint32_t nshards, int precision) {
     if (width == 0 || height == 0 || row_block == 0 || nshards == 0 || nshards > RT_MAX_SHARDS) return false;
-    if (precision != RT_OUT_F64 && precision != RT_OUT_F32) return false;
+    if (precision != RT_OUT_F64 && precision != RT_OUT_F32 && precision != RT_OUT_U8 && precision != RT_OUT_U16)
+        return false;
     return true;
+}
+
+// an integer slab, values buffer or image is aligned to its sample (the float kernels leave their
+// element alignment to the caller, as they always have)
+bool int_aligned(const void *p, int precision) {
+    return precision != RT_OUT_U16 || (reinterpret_cast<uintptr_t>(p) & 1) == 0;
+}
+
+bool is_int(int precision) { return precision == RT_OUT_U8 || precision == RT_OUT_U16; }
+
+// rt_slab_pack's three kernels on an integer slab (T = uint8_t / uint16_t): one pixel per thread
+template <typename T>
+int pack_int(const void *d_slab, const Layout &l, uint64_t valid_px, unsigned char *h, void *d_values, hipStream_t st) {
+    uint32_t *off = reinterpret_cast<uint32_t *>(h + HDR_OFFS);
+    uint64_t *mask = reinterpret_cast<uint64_t *>(h + l.mask_at);
+    const dim3 grid((unsigned)l.nblk), blk(SLAB_BLOCK);
+    hipLaunchKernelGGL(k_mask<T>, grid, blk, 0, st, static_cast<const T *>(d_slab), valid_px, off, mask);
+    SLABCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, off, l.nblk, reinterpret_cast<uint64_t *>(h));
+    SLABCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_compact<T>, grid, blk, 0, st, static_cast<const T *>(d_slab), l.px, off, mask,
+                       static_cast<T *>(d_values));
+    SLABCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// rt_slab_unpack of integer shards: 48 bytes per thread and 16-byte stores when every image row
+// starts on a multiple of 16 bytes and holds whole threads (a 16-byte aligned image whose width is
+// a multiple of 16 pixels of u8 / 8 of u16: 48 bytes), else the element-wise kernel
+template <typename T>
+int unpack_int(const ShardPtrs &sp, const Layout &l, uint32_t width, uint32_t height, uint32_t row_block,
+               uint32_t nshards, void *d_image, hipStream_t st) {
+    constexpr uint32_t G = INT_BYTES / (3 * sizeof(T));
+    const bool wide = width % G == 0 && (reinterpret_cast<uintptr_t>(d_image) & 15) == 0;
+    const uint32_t per_wg = wide ? SLAB_BLOCK * G : SLAB_BLOCK;
+    const uint32_t ncol = (uint32_t)(((uint64_t)width + per_wg - 1) / per_wg);
+    const uint64_t nblocks = (uint64_t)ncol * height;
+    if (nblocks >= (1ull << 31)) return RT_ETOOBIG;
+    if (wide)
+        hipLaunchKernelGGL(k_unpack_int<T>, dim3((unsigned)nblocks), dim3(SLAB_BLOCK), 0, st, sp, l.mask_at, l.px, width,
+                           ncol, row_block, nshards, static_cast<T *>(d_image));
+    else
+        hipLaunchKernelGGL(k_unpack<T>, dim3((unsigned)nblocks), dim3(SLAB_BLOCK), 0, st, sp, l.mask_at, l.px, width,
+                           ncol, row_block, nshards, static_cast<T *>(d_image));
+    SLABCHK(hipGetLastError());
+    return RT_OK;
 }
 
 } // namespace
@@ -295,7 +461,7 @@ size_t rt_slab_header_bytes(uint32_t width, uint32_t height, uint32_t row_block,
 int rt_slab_pack(const void *d_slab, uint32_t width, uint32_t height, uint32_t row_block, uint32_t shard,
                  uint32_t nshards, int precision, void *d_header, void *d_values, void *stream) {
     if (!d_slab || !d_header || !d_values || !args_ok(width, height, row_block, nshards, precision) ||
-        shard >= nshards)
+        shard >= nshards || !int_aligned(d_slab, precision) || !int_aligned(d_values, precision))
         return RT_EBADARG;
     const Layout l = layout(width, rt_shard_rows(height, row_block, nshards));
     if (l.px >= (1ull << 32)) return RT_ETOOBIG;
@@ -307,6 +473,9 @@ int rt_slab_pack(const void *d_slab, uint32_t width, uint32_t height, uint32_t r
     const dim3 grid((unsigned)l.nblk), blk(SLAB_BLOCK);
     const uint64_t valid_px =
         valid_rows(height, row_block, shard, nshards, rt_shard_rows(height, row_block, nshards)) * width;
+    if (is_int(precision))
+        return precision == RT_OUT_U8 ? pack_int<uint8_t>(d_slab, l, valid_px, h, d_values, st)
+                                      : pack_int<uint16_t>(d_slab, l, valid_px, h, d_values, st);
     if (precision == RT_OUT_F32)
         hipLaunchKernelGGL(k_mask<uint32_t>, grid, blk, 0, st, static_cast<const uint32_t *>(d_slab), valid_px, off,
                            mask);
@@ -328,17 +497,21 @@ int rt_slab_pack(const void *d_slab, uint32_t width, uint32_t height, uint32_t r
 
 int rt_slab_unpack(const void *const *d_headers, const void *const *d_values, uint32_t width, uint32_t height,
                    uint32_t row_block, uint32_t nshards, int precision, void *d_image, void *stream) {
-    if (!d_headers || !d_values || !d_image || !args_ok(width, height, row_block, nshards, precision))
+    if (!d_headers || !d_values || !d_image || !args_ok(width, height, row_block, nshards, precision) ||
+        !int_aligned(d_image, precision))
         return RT_EBADARG;
     const Layout l = layout(width, rt_shard_rows(height, row_block, nshards));
     if (l.px >= (1ull << 32)) return RT_ETOOBIG;
     ShardPtrs sp = {};
     for (uint32_t s = 0; s < nshards; ++s) {
-        if (!d_headers[s] || !d_values[s]) return RT_EBADARG;
+        if (!d_headers[s] || !d_values[s] || !int_aligned(d_values[s], precision)) return RT_EBADARG;
         sp.hdr[s] = static_cast<const unsigned char *>(d_headers[s]);
         sp.vals[s] = d_values[s];
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (is_int(precision))
+        return precision == RT_OUT_U8 ? unpack_int<uint8_t>(sp, l, width, height, row_block, nshards, d_image, st)
+                                      : unpack_int<uint16_t>(sp, l, width, height, row_block, nshards, d_image, st);
     // 4 pixels per thread, 16-byte stores: every row of a 16-byte aligned image starts on a multiple
     // of 16 bytes (4 pixels are 48 or 96 bytes); any other image (a view into a larger buffer)
     // takes the element-wise kernel

@@ -18,7 +18,8 @@ import numpy as np
 
 from . import _native as N
 
-PRECISIONS = {"f64": N.RT_OUT_F64, "f32": N.RT_OUT_F32}
+PRECISIONS = {"f64": N.RT_OUT_F64, "f32": N.RT_OUT_F32, "u8": N.RT_OUT_U8, "u16": N.RT_OUT_U16}
+INT_LIMITS = {"u8": 255, "u16": N.RT_MAX_INT_VALUE}  # integer frames: the largest max_value per format
 ORDERS = {"exact": N.RT_ORDER_EXACT, "fast": N.RT_ORDER_FAST}
 
 
@@ -118,7 +119,9 @@ class SlabCodec:
     include/rt_mi355x.h "compact slab transfer"): a slab becomes a fixed-size header (count,
     per-256-pixel offsets, one bit per pixel) plus the non-background pixels' values; rank 0
     decodes every shard straight into the row-major frame (rt_unshard fused with the decode).
-    Device tensors only: there is no host implementation in the product."""
+    ``precision`` "u8" / "u16": integer slabs (quantised where they were rendered), 3 or 6 bytes
+    per non-background pixel; the tensors' dtypes are not looked at, so value buffers and the frame
+    may be byte views.  Device tensors only: there is no host implementation in the product."""
 
     def __init__(self, width: int, height: int, row_block: int, world: int, precision: str):
         self.L = N.lib()
@@ -168,15 +171,21 @@ class CompactGather:
 
     ``first`` = 1: rank 0 renders no rows and only assembles (the codec's shards are ranks 1 ..
     world-1, shard = rank - 1); it submits None and its header in the gather is ignored.
+
+    ``px_elems``: elements of ``dtype`` per pixel in the value buffers (3: one per channel).
+    Integer frames travel as bytes (``dtype`` torch.uint8 for both formats, so the collectives move
+    a type every backend knows): 3 for u8, 6 for u16 samples carried as bytes.
     """
 
     RING = 4
     LAG = 2  # frames between a frame's header gather and its value transfer
 
-    def __init__(self, codec, world, rank, slab_elems, dtype, device, frame, group=None, first=0):
+    def __init__(self, codec, world, rank, slab_elems, dtype, device, frame, group=None, first=0, *,
+                 px_elems: int = 3):
         import torch
         self.torch = torch
         self.codec, self.world, self.rank, self.group = codec, world, rank, group
+        self.px_elems = px_elems
         if first not in (0, 1) or (first == 1 and world < 2):
             raise ValueError("first: 0 (every rank renders) or 1 (rank 0 assembles; world >= 2)")
         self.first = first
@@ -270,7 +279,7 @@ class CompactGather:
                 cev.synchronize()
             counts = [int(c) for c in self.counts[b].tolist()]
             # at least one pixel per message: every rank takes part in every batch
-            n = [max(c, 1) * 3 for c in counts]
+            n = [max(c, 1) * self.px_elems for c in counts]
             ops = []
             if self.rank == 0:
                 for s in range(1, self.world):
@@ -329,8 +338,14 @@ def verify_compact_gather(cg, make_slab, reference, rank, nframes=2, shard=None)
         raise RuntimeError(f"compact gather returned {len(got)} of {nframes} frames")
     for i, f in enumerate(got):
         ref = reference(i)
-        a = f.contiguous().view(torch.int32 if f.dtype == torch.float32 else torch.int64)
-        b = ref.to(f.device).contiguous().view(a.dtype)
+        # floats by their bits (NaN payloads, -0.0); integer frames directly
+        bits = {torch.float32: torch.int32, torch.float64: torch.int64}.get(f.dtype)
+        a, b = f.contiguous(), ref.to(f.device).contiguous()
+        if bits is not None:
+            a, b = a.view(bits), b.view(bits)
+        elif a.dtype != b.dtype or a.shape != b.shape:
+            raise RuntimeError(f"gathered frame {i} is {a.dtype} {tuple(a.shape)}, the one-shard frame "
+                               f"{b.dtype} {tuple(b.shape)}")
         if not torch.equal(a, b):
             bad = int((a != b).any(-1).sum())
             raise RuntimeError(f"gathered frame {i} differs from the one-shard frame in {bad} pixels")
@@ -351,14 +366,28 @@ class FrameRenderer:
     runs its kernels on its slot's stream alone (RT_CFG_SIDE_STREAMS = 0), so the process
     stays within its hardware queues.  ``stream`` is the stream of the last launched frame;
     work on that frame (the gather's pack) goes on it.  ``cull=False`` renders with brute-force
-    scans (RT_CFG_CULL = 0: every object tested by every ray; same bits, many times slower)."""
+    scans (RT_CFG_CULL = 0: every object tested by every ray; same bits, many times slower).
+
+    ``precision`` "u8" / "u16" with ``max_value``: integer frames.  Every slot renders into a
+    binary64 slab of its own and rt_quantize turns the slab's rows inside the image into the slot's
+    integer slab on the same stream: every sample is ``min(trunc(C*max_value), max_value)`` of the
+    binary64 channel, the integer the P3 file prints and rt_render returns.  ``slab`` / ``slabs``
+    are the integer slabs (what the gathers send), ``dtype`` and rank 0's ``frame`` uint8 / uint16.
+    A negative or NaN channel is stored as 0 and counted: ``clamped()``."""
 
     def __init__(self, scene, width: int, height: int, depth: int, *, rank: int = 0, world: int = 1,
                  device: int = 0, row_block: int = 16, precision: str = "f32", order: str = "exact", group=None,
                  levels: bool = False, spp: int = 1, seed: int = 0, inflight: int = 1, cull: bool = True,
-                 priorities="auto", assemble: bool = False):
+                 priorities="auto", assemble: bool = False, max_value: int = 255):
         import torch
         self.torch = torch
+        self.integer = precision in INT_LIMITS
+        if self.integer:  # (before anything is allocated)
+            if isinstance(max_value, bool) or not isinstance(max_value, int) or \
+                    not 0 < max_value <= INT_LIMITS[precision]:
+                raise ValueError(f"badarg: MaxValue of a {precision} frame must be an integer in "
+                                 f"[1, {INT_LIMITS[precision]}], got {max_value!r}")
+        self.max_value = max_value
         self.L = N.lib()
         self.w, self.h, self.depth = width, height, depth
         self.rank, self.world, self.rb, self.group = rank, world, row_block, group
@@ -372,7 +401,8 @@ class FrameRenderer:
         self.spp, self.seed = spp, seed
         self.prec, self.order = PRECISIONS[precision], ORDERS[order]
         self.precision = precision
-        self.dtype = torch.float64 if precision == "f64" else torch.float32
+        self.dtype = {"f64": torch.float64, "f32": torch.float32, "u8": torch.uint8, "u16": torch.uint16}[precision]
+        self._render_prec = N.RT_OUT_F64 if self.integer else self.prec  # (rt_launch writes floats only)
         self.device = torch.device("cuda", device)
         self.rows = shard_rows(height, row_block, self.nshards)
         if inflight < 1 or (inflight > 1 and levels):
@@ -391,6 +421,15 @@ class FrameRenderer:
         self.slabs = [torch.empty((self.rows, width, 3), dtype=self.dtype, device=self.device)
                       for _ in range(inflight)]
         self.slab = self.slabs[0]
+        # integer frames: the binary64 slabs the slots render into, and the renderer's counter of
+        # values stored as 0 because they were negative or NaN (rt_quantize's d_clamped)
+        self._fslabs = self._clamped = None
+        if self.integer:
+            self._fslabs = [torch.empty((self.rows, width, 3), dtype=torch.float64, device=self.device)
+                            for _ in range(inflight)]
+            self._clamped = torch.zeros(1, dtype=torch.int64, device=self.device)
+            g = shard_global_rows(height, row_block, self.nshards, self.shard)
+            self._valid_values = int((g >= 0).sum()) * width * 3  # the slab's rows inside the image: a prefix
         # priorities (inflight > 1): one torch stream priority per slot (lower = higher priority; HIP
         # has two levels, 0 and -1).  "auto": with 4 or more frames in flight and one sample per pixel
         # the first half of the slots run at high priority.  Frames in flight on equal-priority
@@ -432,16 +471,40 @@ class FrameRenderer:
         if not self.renders:  # an assembling rank 0
             return
         lv = self.levels.data_ptr() if self.levels is not None else None
+        self._render(j, self.slab, lv, self.stream)
+
+    def _render(self, j, slab, lv, stream):
+        """Slot j's context renders this rank's shard into `slab` on `stream`; an integer slab is
+        quantised from the slot's binary64 slab on the same stream."""
+        out = self._fslabs[j] if self.integer else slab
         N.check(self.L.rt_launch_spp(self._ps[j], self.w, self.h, self.depth, self.rb, self.shard, self.nshards,
-                                     self.prec, self.order, self.spp, self.seed, self.slab.data_ptr(), lv,
-                                     self.stream.cuda_stream), "rt_launch")
+                                     self._render_prec, self.order, self.spp, self.seed, out.data_ptr(), lv,
+                                     stream.cuda_stream), "rt_launch")
+        if self.integer:
+            self.quantise(j, slab, stream)
+
+    def quantise(self, j, slab, stream):
+        """Integer frames: slot j's binary64 slab to the integer `slab` on `stream` (rt_quantize; part
+        of every launch).  Only the rows inside the image, a prefix of the slab: rt_launch never
+        writes the padding rows, and whatever they hold must not be counted as clamped."""
+        N.check(self.L.rt_quantize(self._fslabs[j].data_ptr(), N.RT_OUT_F64, self._valid_values, self.max_value,
+                                   self.prec, slab.data_ptr(), self._clamped.data_ptr(), stream.cuda_stream),
+                "rt_quantize")
 
     def launch_on(self, j: int):
         """Render a frame on slot j's context, slab and stream (no gather)."""
         stream = self.streams[j] if self.streams is not None else self.torch.cuda.current_stream(self.device)
-        N.check(self.L.rt_launch_spp(self._ps[j], self.w, self.h, self.depth, self.rb, self.shard, self.nshards,
-                                     self.prec, self.order, self.spp, self.seed, self.slabs[j].data_ptr(), None,
-                                     stream.cuda_stream), "rt_launch")
+        self._render(j, self.slabs[j], None, stream)
+
+    def clamped(self) -> int:
+        """Integer frames: the values this rank has stored as 0 because they were negative or NaN,
+        over every frame since construction (waits for the device).  The count is this rank's alone:
+        a caller that wants the frame-wide flag (rt_render's RT_STATS_CLAMPED) reduces it over the
+        ranks.  0 for float frames."""
+        if self._clamped is None:
+            return 0
+        self.torch.cuda.synchronize(self.device)
+        return int(self._clamped.item())
 
     def time_kernels(self, mask: int):
         """Bracket every later launch of the RT_KT_* kernels in `mask` with HIP events on the
@@ -476,6 +539,10 @@ class FrameRenderer:
             for s in self.streams:
                 cur.wait_stream(s)
 
+    def _wire(self, t):
+        """`t` as the collectives move it: integer slabs as bytes (a type every backend knows)."""
+        return t.view(self.torch.uint8) if self.integer and t is not None else t
+
     def gather(self):
         if self.world == 1:
             return self.slab
@@ -483,12 +550,13 @@ class FrameRenderer:
             raise ValueError("an assembling rank 0 takes the compact gather (compact_gather)")
         import torch.distributed as dist
         if self.rank == 0:
-            dist.gather(self.slab, gather_list=list(self.gather_buf.unbind(0)), dst=0, group=self.group)
+            dist.gather(self._wire(self.slab), gather_list=list(self._wire(self.gather_buf).unbind(0)), dst=0,
+                        group=self.group)
             st = self.torch.cuda.current_stream(self.device).cuda_stream
             N.check(self.L.rt_unshard(self.gather_buf.data_ptr(), self.w, self.h, self.rb, self.world, self.prec,
                                       self.frame.data_ptr(), st), "rt_unshard")
             return self.frame
-        dist.gather(self.slab, gather_list=None, dst=0, group=self.group)
+        dist.gather(self._wire(self.slab), gather_list=None, dst=0, group=self.group)
         return None
 
     def step(self):
@@ -505,7 +573,10 @@ class FrameRenderer:
             torch = self.torch
             slabs = [self.slab, torch.empty_like(self.slab)]
             gbufs = [self.gather_buf, torch.empty_like(self.gather_buf)] if self.gather_buf is not None else None
-            self._pipe = SlabPipeline(self.world, self.rank, slabs, gbufs, self._reorder, self.group)
+            self._pipe_slabs = slabs  # (the pipeline's own are their _wire views)
+            self._pipe = SlabPipeline(self.world, self.rank, [self._wire(t) for t in slabs],
+                                      [self._wire(t) for t in gbufs] if gbufs is not None else None, self._reorder,
+                                      self.group)
         return self._pipe
 
     def _reorder(self, gbuf):
@@ -518,7 +589,7 @@ class FrameRenderer:
         """Render the next frame into the free slab and start its gather; returns the previous
         frame on rank 0 once its gather has completed (None otherwise).  drain() finishes."""
         pipe = self.pipeline()
-        self.slab = pipe.slab
+        self.slab = self._pipe_slabs[pipe.i % 2]  # (pipe.slab, in this renderer's dtype)
         self.launch()
         return pipe.submit()
 
@@ -529,8 +600,13 @@ class FrameRenderer:
     def compact_gather(self):
         if self._cg is None:
             codec = SlabCodec(self.w, self.h, self.rb, self.nshards, self.precision)
-            self._cg = CompactGather(codec, self.world, self.rank, self.slab.numel(), self.dtype, self.device,
-                                     self.frame, self.group, first=1 if self.assemble else 0)
+            elems, dtype, frame, px_elems = self.slab.numel(), self.dtype, self.frame, 3
+            if self.integer:  # integer values and the frame as bytes (CompactGather, px_elems)
+                size = self.slab.element_size()
+                elems, dtype, px_elems = elems * size, self.torch.uint8, 3 * size
+                frame = frame.view(self.torch.uint8) if frame is not None else None
+            self._cg = CompactGather(codec, self.world, self.rank, elems, dtype, self.device, frame, self.group,
+                                     first=1 if self.assemble else 0, px_elems=px_elems)
         return self._cg
 
     def step_compact(self):
@@ -539,10 +615,12 @@ class FrameRenderer:
         cg = self.compact_gather()
         self.launch()
         with self.torch.cuda.stream(self.stream):
-            return cg.submit(self.slab if self.renders else None, self.shard)
+            out = cg.submit(self.slab if self.renders else None, self.shard)
+        return self.frame if out is not None else None  # (an integer frame in its own dtype, not cg's bytes)
 
     def drain_compact(self):
-        return self._cg.drain() if self._cg is not None else None
+        out = self._cg.drain() if self._cg is not None else None
+        return self.frame if out is not None else None
 
     def close(self):
         for p in self._ps:

@@ -262,7 +262,11 @@ int rt_reset_contexts(void);
  * (g / row_block) % nshards.  d_out receives the shard's rows packed in order,
  * rt_shard_rows(height,row_block,nshards) rows of width*3 elements; slab rows past
  * the image (the tail of the last row block) are not written, so with nshards = 1 a buffer
- * of `height` rows suffices.  d_levels (optional) gets one byte per slab pixel. */
+ * of `height` rows suffices.  d_levels (optional) gets one byte per slab pixel.
+ * rt_launch / rt_launch_spp write floats only (precision RT_OUT_F64 or RT_OUT_F32).  A resident
+ * integer frame is rt_launch into a binary64 slab followed by rt_quantize of the slab's image
+ * rows (a prefix of the slab) on the same stream; rt_unshard and the compact slab transfer below
+ * take the integer slabs. */
 typedef struct rt_prepared rt_prepared;
 
 int rt_prepare(const rt_elem *scene, uint32_t n_elems, int device, rt_prepared **out);
@@ -275,7 +279,9 @@ int rt_launch_spp(rt_prepared *p, uint32_t width, uint32_t height, uint32_t dept
                   uint32_t row_block, uint32_t shard, uint32_t nshards, int precision, int order,
                   uint32_t spp, uint64_t seed, void *d_out, uint8_t *d_levels, void *stream);
 /* Reassemble nshards gathered slabs (d_slabs = [nshards][shard_rows][W*3]) into the
- * row-major image d_image ([H][W*3]), on `stream`. */
+ * row-major image d_image ([H][W*3]), on `stream`.  precision: the slabs' element, any of
+ * RT_OUT_F64, RT_OUT_F32, RT_OUT_U8, RT_OUT_U16 (rows of W*3 elements of 8, 4, 1 or 2 bytes); the
+ * call is device copies of whole rows, so no alignment is asked of an integer slab. */
 int rt_unshard(const void *d_slabs, uint32_t width, uint32_t height, uint32_t row_block,
                uint32_t nshards, int precision, void *d_image, void *stream);
 int rt_release(rt_prepared *p);
@@ -322,6 +328,11 @@ int rt_kernel_time(rt_prepared *p, int kernel, double *total_ms, uint64_t *launc
  * count*3 values of the slab's precision, the non-zero pixels in slab order.  The round trip
  * is exact (bit patterns are copied; a pixel is zero iff its three channels are all-zero
  * bits).  Slab rows past the image are not read and decode as zero.
+ * Integer slabs (precision RT_OUT_U8 / RT_OUT_U16: a binary64 slab quantised by rt_quantize on the
+ * rank that rendered it) take the same header; their values are the non-zero pixels' three
+ * samples, 3 bytes per pixel for RT_OUT_U8 and 6 (native endian) for RT_OUT_U16.  A pixel is
+ * non-zero iff any of its three samples is (a 16-bit sample such as 0x0100 or 0x0001 is), so the
+ * round trip is exact for them too.
  * rt_slab_header_bytes: header size for one shard of this frame (0 for bad arguments).
  * rt_slab_pack: encode shard `shard`'s slab on `stream`; d_values needs room for every slab
  *   pixel (shard_rows*width*3 elements) in the worst case.
@@ -332,6 +343,12 @@ int rt_kernel_time(rt_prepared *p, int kernel, double *total_ms, uint64_t *launc
  *   multiple of 256), a slab, a values buffer and d_image aligned to their element (4 bytes for
  *   RT_OUT_F32, 8 for RT_OUT_F64).  A 16-byte aligned d_image whose width is a multiple of 4 is
  *   written with 16-byte stores; any other one element by element (slower, same bytes).
+ *   Integer formats: RT_OUT_U8 buffers may start anywhere; an RT_OUT_U16 slab, values buffer or
+ *   d_image that is not 2-byte aligned is RT_EBADARG (checked with the other arguments, before any
+ *   HIP call).  A values buffer need not be aligned any further (rank 0's are rows of a byte
+ *   matrix): the decode reads it the same way at every alignment.  A 16-byte aligned d_image whose
+ *   width is a multiple of 16 (RT_OUT_U8) or 8 (RT_OUT_U16) pixels is decoded 48 bytes per thread
+ *   and written with 16-byte stores; any other one sample at a time (slower, same bytes).
  * A pack owns its header and values buffers until its kernels have run: the block offsets are
  *   scanned in place in the header, so two packs in flight (on different streams) must not share
  *   a header or a values buffer, and neither may be read before the pack's stream reaches it. */

@@ -11,7 +11,14 @@ Each is measured here on one device (no RCCL: the transfer is counted, not run) 
 step compared with the N = 1 frame (bench.py's configuration: 4 frames in flight) and north_star's
 ">= 6x further at 8 GPUs".
 
-    python scripts/n8_floor.py [--scene s64] [--size 4096] [--depth 5] [--reps 40]
+    python scripts/n8_floor.py [--scene s64] [--size 4096] [--depth 5] [--reps 40] [--precision f32]
+
+--precision u8 / u16: integer frames through the gather (dist.FrameRenderer renders binary64 and
+quantises each shard where it is rendered; the codec moves 3 or 6 bytes per non-background pixel).
+Every render above then includes its quantise pass, and the record adds, per shard, quantise + pack
+alone.  The codec alone (pack per shard, the decode of all shards) is timed with HIP events over
+several windows, median reported, with the decode's algorithmic bytes per second: the frame written
+plus the values and headers read.
 """
 import argparse
 import json
@@ -35,6 +42,9 @@ def main():
     ap.add_argument("--inflight", type=int, default=3, help="frames in flight per rank (bench.py at N > 1: 3)")
     ap.add_argument("--sweep", default="2,3,4,6,8", help="frames in flight tried for shard 0")
     ap.add_argument("--world", type=int, default=8)
+    ap.add_argument("--precision", default="f32", choices=["f32", "u8", "u16"],
+                    help="the gathered frame's format (u8 / u16: quantised per shard, max_value the format's largest)")
+    ap.add_argument("--codec-reps", type=int, default=500, help="launches per timing window of the codec alone")
     a = ap.parse_args()
     import torch
 
@@ -43,8 +53,29 @@ def main():
     W = H = a.size
     scene = scenes.named(a.scene)
     ns = a.world
-    res = {"scene": a.scene, "size": a.size, "depth": a.depth, "world": ns,
+    prec = a.precision
+    integer = prec != "f32"
+    esz = {"f32": 4, "u8": 1, "u16": 2}[prec]          # bytes per channel
+    kw = dict(precision=prec, max_value={"u8": 255, "u16": 65535}[prec]) if integer else dict(precision=prec)
+    # codec buffers: float32 values, or bytes for the integer formats (as dist.CompactGather moves them)
+    buf_dt, buf_per_ch = (torch.uint8, esz) if integer else (torch.float32, 1)
+    res = {"scene": a.scene, "size": a.size, "depth": a.depth, "world": ns, "precision": prec,
            "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
+
+    def events_ms(fn, windows=5):
+        """ms per call of fn, back to back on the current stream: the median of `windows` windows of
+        --codec-reps calls each between two HIP events (after one untimed window), and the windows."""
+        ms = []
+        for k in range(windows + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.codec_reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if k:
+                ms.append(e0.elapsed_time(e1) / a.codec_reps)
+        return round(sorted(ms)[len(ms) // 2], 5), [round(x, 5) for x in ms]
 
     def per_frame(fr, extra=None, reps=a.reps):
         """ms per frame with fr's frames in flight (fr.launch cycles its slots); extra(i) runs after
@@ -65,7 +96,7 @@ def main():
         return (time.perf_counter() - t0) / reps * 1e3
 
     # N = 1 as bench.py runs it (4 in flight, auto priorities), after a second of frames (clock ramp)
-    fr1 = FrameRenderer(scene, W, H, a.depth, precision="f32", inflight=4)
+    fr1 = FrameRenderer(scene, W, H, a.depth, inflight=4, **kw)
     t0 = time.perf_counter()
     while time.perf_counter() - t0 < 1.0:
         for _ in range(8):
@@ -75,24 +106,25 @@ def main():
     fr1.close()
     # shard 0 of ns with k frames in flight (more frames hide more of a small shard's latency-bound tail)
     sweep = {}
-    for k in [int(x) for x in a.sweep.split(",")]:
-        fk = FrameRenderer(scene, W, H, a.depth, rank=0, world=ns, precision="f32", inflight=k)
+    for k in [int(x) for x in a.sweep.split(",") if x]:
+        fk = FrameRenderer(scene, W, H, a.depth, rank=0, world=ns, inflight=k, **kw)
         sweep[k] = round(per_frame(fk), 4)
         fk.close()
     res["shard0_frame_ms_by_inflight"] = sweep
 
-    codec = SlabCodec(W, H, 16, ns, "f32")
+    codec = SlabCodec(W, H, 16, ns, prec)
     rows = fr_rows = None
     shard_ms, shard_pack_ms, values_bytes = [], [], []
+    pack_alone, quant_pack_alone = [], []
     headers, values = [], []
     for s in range(ns):
-        fr = FrameRenderer(scene, W, H, a.depth, rank=s, world=ns, precision="f32", inflight=a.inflight)
+        fr = FrameRenderer(scene, W, H, a.depth, rank=s, world=ns, inflight=a.inflight, **kw)
         fr_rows = fr.rows
         shard_ms.append(round(per_frame(fr), 4))
         # one header / values buffer per slot: packs of frames in flight must not share them (a
         # header packed by two streams at once is inconsistent, as dist.CompactGather's ring avoids)
         hdrs = [torch.empty(codec.header_bytes, dtype=torch.uint8, device="cuda") for _ in fr._ps]
-        vals = [torch.empty(fr.rows * W * 3, dtype=torch.float32, device="cuda") for _ in fr._ps]
+        vals = [torch.empty(fr.rows * W * 3 * buf_per_ch, dtype=buf_dt, device="cuda") for _ in fr._ps]
 
         def pack(i, fr=fr, hdrs=hdrs, vals=vals, s=s):
             j = (fr.n - 1) % len(fr._ps)  # the slot fr.launch() just used
@@ -102,19 +134,20 @@ def main():
         torch.cuda.synchronize()
         hdr, val = hdrs[0], vals[0]
         cnt = int(hdr[:8].view(torch.int64).item())
-        values_bytes.append(cnt * 3 * 4)
+        values_bytes.append(cnt * 3 * esz)
         headers.append(hdr.clone())
         values.append(val.clone())
+        # the pack alone, and for an integer format the shard's quantise + pack (what a rank adds to
+        # its render), HIP events, back to back on one stream; the slab holds the shard's last frame
+        pack_alone.append(events_ms(lambda: codec.pack(fr.slabs[0], s, hdr, val))[0])
+        if integer:
+            def quant_pack():
+                fr.quantise(0, fr.slabs[0], torch.cuda.current_stream())
+                codec.pack(fr.slabs[0], s, hdr, val)
+            quant_pack_alone.append(events_ms(quant_pack)[0])
         if s == 0:
             pack_bufs = (hdrs, vals)
-            # the pack alone (HIP events, back to back on one stream)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.reps):
-                codec.pack(fr.slabs[0], 0, hdr, val)
-            e1.record()
-            torch.cuda.synchronize()
-            res["pack_ms"] = round(e0.elapsed_time(e1) / a.reps, 4)
+            res["pack_ms"] = pack_alone[0]
             fr0 = fr
         else:
             fr.close()
@@ -122,14 +155,15 @@ def main():
     res["shard_rows"] = rows
     res["shard_frame_ms"] = shard_ms
     res["shard_frame_pack_ms"] = shard_pack_ms
-    frame = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(a.reps):
-        codec.unpack(headers, values, frame)
-    e1.record()
-    torch.cuda.synchronize()
-    res["unpack8_ms"] = round(e0.elapsed_time(e1) / a.reps, 4)
+    res["shard_pack_alone_ms"] = pack_alone
+    if integer:
+        res["shard_quantise_pack_alone_ms"] = quant_pack_alone
+    frame = torch.empty((H, W, 3 * buf_per_ch), dtype=buf_dt, device="cuda")
+    res["unpack8_ms"], res["unpack8_ms_windows"] = events_ms(lambda: codec.unpack(headers, values, frame))
+    # the decode's algorithmic bytes: the frame written once, every shard's values and header read once
+    decode_bytes = H * W * 3 * esz + sum(values_bytes) + ns * codec.header_bytes
+    res["unpack8_algorithmic_bytes"] = decode_bytes
+    res["unpack8_tb_per_s"] = round(decode_bytes / (res["unpack8_ms"] * 1e-3) / 1e12, 3)
     # rank 0: its shard rendered and packed with frames in flight, all 8 shards decoded beside it
     xs = torch.cuda.Stream()
 
