@@ -85,7 +85,7 @@ __device__ __forceinline__ void stage_tables(const Scene &S) {
 }
 
 // Diagnostic build only (-DRT_STATS): per-wave event counters read back with rt_debug_stats().
-#define RT_NSTATS 20
+#define RT_NSTATS 24
 #ifdef RT_STATS
 __device__ unsigned long long g_stats[RT_NSTATS];
 #define RT_STAT(i, v)                                                                                              \
@@ -100,7 +100,8 @@ __device__ unsigned long long g_stats[RT_NSTATS];
 #endif
 enum { ST_WAVES, ST_NEAR_PRE, ST_NEAR_PRE_CAND, ST_NEAR_GEN, ST_NEAR_GEN_CAND, ST_SHADOW, ST_SHADOW_CAND,
        ST_SHADOW_ITER, ST_SHADE, ST_SHADOW_CONE_ON, ST_BEAM_ON, ST_SHADOW_LANES, ST_NEAR_LANES, ST_BVH_SCANS,
-       ST_BVH_ITER, ST_BVH_LEAF, ST_BVH_ITER_LANES, ST_BVH_LEAF_LANES };
+       ST_BVH_ITER, ST_BVH_LEAF, ST_BVH_ITER_LANES, ST_BVH_LEAF_LANES,
+       ST_PRIM_WAVES, ST_PRIM_EMPTY, ST_PRIM_FILL }; // k_primary: its waves, those with all-zero masks, those filling wide
 
 // ---- Beam culling ----------------------------------------------------------------------------
 // A wave's 64 rays are coherent (an 8x8 pixel tile; shadow rays of one light; their

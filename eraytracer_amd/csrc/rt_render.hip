@@ -668,6 +668,7 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
     // the primary rays' candidate masks of the whole slab (k_pmask), recomputed only when the
     // frame geometry or the scene changed (or after rt_trim)
     const unsigned long long *pmask = nullptr;
+    const unsigned short *pempty = nullptr; // after the masks: one byte per half-tile, 1 = every mask zero
     if (p->hdr.beam_ok && D > 0) {
         const int slab_all = (int)rt_shard_rows(H, rb, ns);
         const size_t nhalf = (size_t)tiles_x * ((slab_all + TILE - 1) / TILE) * 2;
@@ -677,18 +678,21 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
             // New masks (and perhaps a new buffer): a frame graph captured with the old ones holds
             // no k_pmask launch and would read these, so it is invalidated (gen).
             ++p->gen;
-            if ((rc = grow(p, rt_prepared::W_PMASK, nhalf * p->hdr.n_chunk * 8)) != RT_OK) return rc;
+            if ((rc = grow(p, rt_prepared::W_PMASK, nhalf * p->hdr.n_chunk * 8 + nhalf)) != RT_OK) return rc;
             const dim3 pg((unsigned)std::min<size_t>(4096, (nhalf + 3) / 4));
             KtScope kt(p, RT_KT_PMASK, st);
             with_bool(spp > 1, [&](auto ss) {
                 hipLaunchKernelGGL(k_pmask<decltype(ss)::value>, pg, dim3(256), 0, st, p->hdr, p->d_tab, p->d_itab, W, H,
-                                   rb, sh, ns, slab_all, (int)nhalf, p->buf<unsigned long long>(rt_prepared::W_PMASK));
+                                   rb, sh, ns, slab_all, (int)nhalf, p->buf<unsigned long long>(rt_prepared::W_PMASK),
+                                   reinterpret_cast<unsigned char *>(p->buf<unsigned long long>(rt_prepared::W_PMASK) +
+                                                           nhalf * p->hdr.n_chunk));
             });
             HIPCHK(hipGetLastError());
             std::memcpy(p->pmask_key, key, sizeof(key));
             p->pmask_valid = true;
         }
         pmask = p->buf<unsigned long long>(rt_prepared::W_PMASK);
+        pempty = reinterpret_cast<const unsigned short *>(pmask + nhalf * p->hdr.n_chunk);
     }
     // streams of the shading pass: level 0 (the bulk) beside the whole reflection chain, the
     // next levels each on their own, so no level waits for another's shading
@@ -745,7 +749,7 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
             with_bool(lv0 != nullptr, [&](auto has_lv) { // (without lv0 there is no lv either)
                 hipLaunchKernelGGL((k_primary<PREC, decltype(has_lv)::value>), grid, dim3(PRIMARY_BLOCK), 0, st, p->hdr,
                                    p->d_tab, p->d_itab, W, H, D, rb, sh, ns, rows, row0, o, lv0, q, d_counts, ntiles, spp,
-                                   sample, seed, acc_p, pmask, nitems);
+                                   sample, seed, acc_p, pmask, pempty, nitems);
             });
         }
         HIPCHK(hipGetLastError());

@@ -369,11 +369,11 @@ __device__ __forceinline__ Beam32 make_beam_corners32(const SceneHdr &h, int W, 
 }
 
 // One wave per 8x16 pixel block (k_primary's half-tiles, numbered 2 * tile + half over the whole
-// slab); masks[block * n_chunk + chunk].
+// slab); masks[block * n_chunk + chunk], and pe[block] = 1 when every one of them is zero.
 template <bool JITTER>
 __global__ __launch_bounds__(256) void k_pmask(SceneHdr hdr, const double *__restrict__ tab, const int *__restrict__ itab,
                                                int W, int H, int rb, int shard, int nshards, int slab_rows, int nhalf,
-                                               unsigned long long *__restrict__ pm) {
+                                               unsigned long long *__restrict__ pm, unsigned char *__restrict__ pe) {
     const Scene S{hdr, tab, itab};
     const int lane = threadIdx.x & 63;
     const int tiles_x = (W + TILE - 1) / TILE;
@@ -393,10 +393,13 @@ __global__ __launch_bounds__(256) void k_pmask(SceneHdr hdr, const double *__res
             const D3 d0 = primary_dir(hdr, W, H, 1, 0, 0, x, gy0), d1 = primary_dir(hdr, W, H, 1, 0, 0, x, gy1);
             b = make_beam_pair32(hdr, a0, d0, a1, d1);
         }
+        unsigned long long any = 0;
         for (int chunk = 0; chunk < hdr.n_sph; chunk += 64) {
             const unsigned long long m = b.on ? cull_chunk32_org(S, b, chunk, 0) : chunk_all(hdr.n_sph, chunk);
             if (lane == 0) pm[(size_t)hw * hdr.n_chunk + (chunk >> 6)] = m;
+            any |= m;
         }
+        if (lane == 0) pe[hw] = any == 0; // no candidate in any chunk: k_primary reads the tile's two bytes at once
     }
 }
 
@@ -444,7 +447,8 @@ inline size_t level_counts(int nlev) { return (size_t)std::max(LEVEL_COUNTS, (nl
 #endif
 constexpr int PRIMARY_GRID = RT_PRIMARY_GRID;
 #ifndef RT_PRIMARY_WAVES
-#define RT_PRIMARY_WAVES 0 // waves per SIMD k_primary is compiled for (0: the compiler's choice, 85 VGPRs = 5)
+#define RT_PRIMARY_WAVES 0 // waves per SIMD k_primary is compiled for (0: the compiler's choice, 79-80 VGPRs = 6;
+                           // 7 spills 3-4 VGPRs to scratch)
 #endif
 #if RT_PRIMARY_WAVES > 0
 #define RT_PRIMARY_BOUNDS __launch_bounds__(PRIMARY_BLOCK, RT_PRIMARY_WAVES)
@@ -460,9 +464,9 @@ __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restri
                                                            int spp, int sample, unsigned long long seed,
                                                            double *__restrict__ acc,
                                                            const unsigned long long *__restrict__ pmask,
-                                                           int *__restrict__ nitems) {
+                                                           const unsigned short *__restrict__ pempty, int *__restrict__ nitems) {
     // this pass covers slab rows [row0, row0 + rows); out/levels point at slab row row0; pmask (or
-    // null): k_pmask's candidate masks over the whole slab
+    // null): k_pmask's candidate masks over the whole slab, pempty its all-zero flags per tile (both halves')
     __shared__ int s_cnt[2][PRIMARY_BLOCK / 64]; // per tile, alternating (one barrier per tile)
     const Scene S{hdr, tab, itab};
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -472,50 +476,120 @@ __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restri
         for (int i = tid; i < LEVEL_COUNTS || i < depth; i += PRIMARY_BLOCK) nitems[i] = 0; // level_counts(depth)
     const D3 cam = {hdr.cam_x, hdr.cam_y, hdr.cam_z};
     const int tiles_x = (W + TILE - 1) / TILE;
+    const PassGeom geom{W, H, rb, shard, nshards, row0, spp, sample, seed, acc};
+    // Sphere-only scenes with masks: a half-tile whose candidate masks are all zero has no ray that
+    // can hit anything (the walk would visit nothing, and there is nothing else to scan), so its wave
+    // traces none.  Without masks (brute force, no beams) and in mixed scenes no half-tile is empty.
+    const bool may_skip = pmask != nullptr && hdr.cull_ok && (hdr.n_tri | hdr.n_pl) == 0;
+    // A tile with both halves empty is written with 16-byte stores when the pass writes the frame
+    // itself (no running sum) and every row of it starts on a 16-byte boundary.
+    constexpr int ESZ = PREC == RT_OUT_F64 ? 8 : 4;
+    const size_t pitch = (size_t)W * 3 * ESZ;
+    const bool wide_ok = acc == nullptr && ((reinterpret_cast<uintptr_t>(out) | pitch) & 15) == 0;
     int it = 0;
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, it ^= 1) {
+    // The next tile's flags are loaded a tile ahead of their use (the two halves' in one 16-bit word: one
+    // VGPR holds them across the ray work).  (A block taking two adjacent tiles in a row, so that one CU
+    // writes whole 128-byte lines of a binary32 frame, measured no better: profiles/primary_tiles_ab.txt.)
+    auto flags_of = [&](int t) { return may_skip && t < ntiles ? (unsigned)pempty[(row0 / TILE) * tiles_x + t] : 0u; };
+    unsigned flags = flags_of(blockIdx.x), flags_next;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, flags = flags_next) {
+        flags_next = flags_of(tile + (int)gridDim.x);
         const int by = tile / tiles_x, bx = tile - by * tiles_x;
         const int x = bx * TILE + wave * 8 + (lane & 7);
         // slab row -> image row through the shard interleave without a per-lane integer division:
         // the tile's first slab row is split once (wave-uniform), the lane's offset (< 16) added
         const int ly_base = row0 + by * TILE;
         const int q_base = ly_base / rb, r_base = ly_base - q_base * rb;
-        auto pixel = [&](int lr, bool &inside, bool &active, D3 &d) {
+        auto image_row = [&](int lr) {
             int rr = r_base + (lr - by * TILE), qq = q_base; // slab row row0 + lr
             while (rr >= rb) { // offset < 16: at most 16 / rb + 1 steps
                 rr -= rb;
                 ++qq;
             }
-            const int gy = (qq * nshards + shard) * rb + rr;
-            // slab rows past the image (the last row block's tail) are never written: a
-            // single-shard caller's buffer need only hold the image's rows
+            return (qq * nshards + shard) * rb + rr;
+        };
+        // slab rows past the image (the last row block's tail) are never written: a
+        // single-shard caller's buffer need only hold the image's rows
+        auto row_inside = [&](int lr) { return lr < rows && image_row(lr) < H; };
+        const int lr0 = by * TILE + (lane >> 3), lr1 = lr0 + 8;
+        // (the wave's entry at a wave-uniform address; both waves read both halves' flags)
+        const int wv = __builtin_amdgcn_readfirstlane(wave); // (a scalar: what it selects stays wave-uniform)
+        const unsigned long long *pm =
+            pmask ? pmask + ((size_t)((row0 / TILE) * tiles_x + tile) * 2 + wv) * hdr.n_chunk : nullptr;
+        const unsigned fl = __builtin_amdgcn_readfirstlane(flags);
+        const bool empty0 = (fl & 0xffu) != 0, empty1 = (fl >> 8) != 0;
+        const bool mine_empty = wv ? empty1 : empty0, other_empty = wv ? empty0 : empty1;
+        RT_STAT(ST_WAVES, 1);
+        RT_STAT(ST_PRIM_WAVES, 1);
+        if (mine_empty) {
+            RT_STAT(ST_PRIM_EMPTY, 1);
+            const bool fill = other_empty && wide_ok;
+            if (fill) {
+                RT_STAT(ST_PRIM_FILL, 1);
+                // the tile's columns inside the image: a multiple of 16 bytes per row, as the pitch is
+                const int nvec = min(TILE, W - bx * TILE) * 3 * ESZ / 16; // 12 (f32) or 24 (f64) for a full tile
+                constexpr int LPR = PREC == RT_OUT_F64 ? 32 : 16;         // lanes per row: the first nvec of them store
+                // (the lane's place from an opaque lane index: row offsets derived from tid were hoisted out of
+                // the tile loop into VGPRs that stay live across the ray work: 85-88 VGPRs, 5 waves per SIMD)
+                const int ft = wv * 64 + lane_id();
+                const int v = ft & (LPR - 1);
+                char *const col0 = static_cast<char *>(out) + (size_t)bx * TILE * 3 * ESZ;
+                // (image rows grow with slab rows: the tile's last row inside means all of them, a scalar test)
+                const bool all_rows = row_inside(by * TILE + TILE - 1);
+                for (int r = ft / LPR; r < TILE; r += PRIMARY_BLOCK / LPR) {
+                    const int lr = by * TILE + r;
+                    if (v < nvec && (all_rows || row_inside(lr)))
+                        *reinterpret_cast<uint4 *>(col0 + (size_t)lr * pitch + (size_t)v * 16) = uint4{0u, 0u, 0u, 0u};
+                }
+            }
+            if (!fill || LEVELS) {
+                const bool in0 = x < W && row_inside(lr0), in1 = x < W && row_inside(lr1);
+                const size_t pix0 = (size_t)lr0 * W + x, pix1 = (size_t)lr1 * W + x;
+                if (!fill) {
+                    if (in0) put_background<PREC>(out, geom, pix0);
+                    if (in1) put_background<PREC>(out, geom, pix1);
+                }
+                if (LEVELS && in0) levels[pix0] = 0;
+                if (LEVELS && in1) levels[pix1] = 0;
+            }
+            // (an empty wave has no count to give, and needs the other's only for the tile's total:
+            // the live wave of such a tile writes the counts)
+            if (other_empty)
+                for (int l = tid; l < depth; l += PRIMARY_BLOCK) cnt[(size_t)l * ntiles + tile] = 0;
+            continue;
+        }
+        auto pixel = [&](int lr, bool &inside, bool &active, D3 &d) {
+            const int gy = image_row(lr);
             inside = x < W && lr < rows && gy < H;
             active = inside && depth > 0;
             d = primary_dir(hdr, W, H, spp, sample, seed, x, gy);
         };
-        const int lr0 = by * TILE + (lane >> 3), lr1 = lr0 + 8;
         bool in0, in1, a0, a1;
         D3 d0, d1;
         pixel(lr0, in0, a0, d0);
         pixel(lr1, in1, a1, d1);
-        RT_STAT(ST_WAVES, 1);
         int id0, id1;
         double t0, t1;
-        // (the wave's entry at a wave-uniform address: scalar loads)
-        const unsigned long long *pm =
-            pmask ? pmask + ((size_t)((row0 / TILE) * tiles_x + tile) * 2 + __builtin_amdgcn_readfirstlane(wave)) * hdr.n_chunk
-                  : nullptr;
         if (hdr.cull_ok)
             nearest_pair<true>(S, 0, cam, d0, d1, a0, a1, id0, t0, id1, t1, pm);
         else
             nearest_pair<false>(S, 0, cam, d0, d1, a0, a1, id0, t0, id1, t1, pm);
         const bool h0 = id0 >= 0, h1 = id1 >= 0;
-        // compact the tile's hits: wave counts in LDS, prefix over the two waves
+        // compact the tile's hits: wave counts in LDS, prefix over the two waves.  A tile with an
+        // empty half has one wave's hits only: no exchange and no barrier (both waves see both
+        // halves' masks, so they agree on which tiles meet at the barrier, and `it` alternates
+        // over those tiles only).
         const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1);
-        if (lane == 0) s_cnt[it][wave] = __popcll(m0) + __popcll(m1);
-        __syncthreads();
-        const int c0 = s_cnt[it][0], c1 = s_cnt[it][1];
-        const int before = wave ? c0 : 0, total = c0 + c1;
+        const int mine = __popcll(m0) + __popcll(m1);
+        int before = 0, total = mine;
+        if (!other_empty) {
+            if (lane == 0) s_cnt[it][wave] = mine;
+            __syncthreads();
+            const int c0 = s_cnt[it][0], c1 = s_cnt[it][1];
+            before = wave ? c0 : 0;
+            total = c0 + c1;
+            it ^= 1;
+        }
         const unsigned long long lt = (1ull << lane) - 1;
         auto emit = [&](bool hit, bool inside, const D3 &d, int id, double t, int lr, int slot) {
             const size_t pix = (size_t)lr * W + x;
@@ -524,14 +598,16 @@ __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restri
                 r.pix = (int)pix; r.obj = id; r.t = t;
                 reinterpret_cast<Rec0 *>(q)[slot] = r; // the rest is rebuilt by load_rec0
             } else if (inside) {
-                put_background<PREC>(out, PassGeom{W, H, rb, shard, nshards, row0, spp, sample, seed, acc}, pix);
+                put_background<PREC>(out, geom, pix);
             }
             if (LEVELS && inside) levels[pix] = hit ? 1 : 0;
         };
         const int base = tile * TILE_SLOTS + before;
         emit(h0, in0, d0, id0, t0, lr0, base + __popcll(m0 & lt));
         emit(h1, in1, d1, id1, t1, lr1, base + __popcll(m0) + __popcll(m1 & lt));
-        for (int l = tid; l < depth; l += PRIMARY_BLOCK) cnt[(size_t)l * ntiles + tile] = l == 0 ? total : 0;
+        // (the tile's counts: by both waves' lanes, or by the live wave's alone)
+        for (int l = other_empty ? lane : tid; l < depth; l += other_empty ? 64 : PRIMARY_BLOCK)
+            cnt[(size_t)l * ntiles + tile] = l == 0 ? total : 0;
     }
 }
 

@@ -5,7 +5,7 @@ from eraytracer_amd import _native as N, scenes
 from eraytracer_amd.raytracer import render
 NAMES = ["waves", "near_pre", "near_pre_cand", "near_gen", "near_gen_cand", "shadow", "shadow_cand", "shadow_iter",
          "shade", "shadow_cone_on", "beam_on", "shadow_lanes", "near_lanes", "bvh_scans", "bvh_iter", "bvh_leaf",
-         "bvh_iter_lanes", "bvh_leaf_lanes"]
+         "bvh_iter_lanes", "bvh_leaf_lanes", "prim_waves", "prim_empty", "prim_fill"]
 L = N.lib()
 L.rt_debug_stats.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int, ctypes.c_int]
 buf = (ctypes.c_ulonglong * len(NAMES))()
@@ -19,3 +19,6 @@ for name, size, depth, order in CASES:
     d = dict(zip(NAMES, list(buf)))
     w = d["waves"]
     print(name, size, depth, json.dumps({k: round(v / w, 3) for k, v in d.items()}))
+    pw = max(d["prim_waves"], 1)  # k_primary's waves: those with all-zero masks, and those of tiles filled wide
+    print(name, size, depth, "k_primary waves", d["prim_waves"], "empty", round(d["prim_empty"] / pw, 4), "wide fill",
+          round(d["prim_fill"] / pw, 4))
