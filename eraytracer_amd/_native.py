@@ -43,7 +43,7 @@ RT_ENGINE_WAVE, RT_ENGINE_FUSED = 0, 1
 # every symbol include/rt_mi355x.h declares (tests/test_boundary.py checks the export list)
 EXPORTS = (
     "rt_abi_version", "rt_strerror", "rt_device_count", "rt_scene_check", "rt_scene_canon",
-    "rt_render", "rt_prepare", "rt_shard_rows", "rt_launch", "rt_launch_spp", "rt_unshard", "rt_configure", "rt_release",
+    "rt_render", "rt_prepare", "rt_shard_rows", "rt_launch", "rt_launch_spp", "rt_launch_window", "rt_unshard", "rt_configure", "rt_release",
     "rt_update_scene",
     "rt_ppm_bound", "rt_ppm_format", "rt_render_ppm_file",
     "rt_quantize", "rt_render_rawppm_file",
@@ -96,7 +96,10 @@ class RtOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("first_dev", ctypes.c_int32), ("ndev", ctypes.c_int32),
                 ("precision", ctypes.c_int32), ("order", ctypes.c_int32), ("row_block", ctypes.c_uint32),
                 ("out_levels", ctypes.c_void_p), ("spp", ctypes.c_uint32), ("nshards", ctypes.c_uint32),
-                ("seed", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("max_value", ctypes.c_uint32)]
+                ("seed", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("max_value", ctypes.c_uint32),
+                # the pixel window (RT_WINDOW in the header); all zero = the whole frame
+                ("win_x0", ctypes.c_uint32), ("win_y0", ctypes.c_uint32), ("win_w", ctypes.c_uint32),
+                ("win_h", ctypes.c_uint32)]
 
 
 class RtStats(ctypes.Structure):
@@ -143,6 +146,8 @@ def lib() -> ctypes.CDLL:
     L.rt_shard_rows.argtypes = [u32, u32, u32]
     L.rt_launch.argtypes = [vp, u32, u32, u32, u32, u32, u32, i32, i32, vp, vp, vp]
     L.rt_launch_spp.argtypes = [vp, u32, u32, u32, u32, u32, u32, i32, i32, u32, ctypes.c_uint64, vp, vp, vp]
+    L.rt_launch_window.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, i32, i32, u32, ctypes.c_uint64,
+                                   vp, vp, vp]
     L.rt_ppm_bound.restype = ctypes.c_size_t
     L.rt_ppm_bound.argtypes = [u32, u32, u32]
     L.rt_ppm_format.argtypes = [vp, i32, u32, u32, u32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), vp]

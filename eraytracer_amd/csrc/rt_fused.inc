@@ -11,8 +11,10 @@ template <int ORDER, int PREC, bool LEVELS, bool GENPOW, bool NB>
 __global__ __launch_bounds__(256, NB ? RT_FUSED_NB_WAVES : RT_WAVES_PER_SIMD) void k_render(SceneHdr hdr, const double *__restrict__ tab,
                                                   const int *__restrict__ itab, int W, int H, int depth, int rb,
                                                   int shard, int nshards, int row0, int row_end, void *__restrict__ out,
-                                                  uint8_t *__restrict__ levels, int levels_hit) {
-    // this launch covers slab rows [row0, row_end); out / levels point at slab row 0
+                                                  uint8_t *__restrict__ levels, int levels_hit, int IW, int IH, int x0,
+                                                  int y0) {
+    // this launch covers slab rows [row0, row_end); out / levels point at slab row 0.  W x H is the
+    // raster, a window of the IW x IH image at (x0, y0): only the primary ray reads the image's geometry
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const Scene S{hdr, tab, itab};
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -31,7 +33,7 @@ __global__ __launch_bounds__(256, NB ? RT_FUSED_NB_WAVES : RT_WAVES_PER_SIMD) vo
     RT_STAT(ST_WAVES, 1);
 
     // primary ray: ray_through_pixel/3 (:510-511) at {X/Width, Y/Height} (:112)
-    const double X = div_n((double)x, (double)W), Y = div_n((double)gy, (double)H); // == / (W, H <= 2^20)
+    const double X = div_n((double)(x0 + x), (double)IW), Y = div_n((double)(y0 + gy), (double)IH); // == / (IW, IH <= 2^20)
     const double px = 0.0 + ((X - 0.5) * hdr.screen_w + hdr.sx);
     const double py = (Y - 0.5) * hdr.screen_h + hdr.sy;
     const D3 cam = {hdr.cam_x, hdr.cam_y, hdr.cam_z};

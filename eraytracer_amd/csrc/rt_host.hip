@@ -495,8 +495,9 @@ int rt_reset_contexts(void) {
     return busy;
 }
 
-int rt_render(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height, uint32_t depth, const rt_opts *opts,
+int rt_render(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, uint32_t depth, const rt_opts *opts,
               void *out_rgb, rt_stats *stats) {
+    uint32_t width = img_w, height = img_h; // the window's from the window checks on
     auto t_begin = std::chrono::steady_clock::now();
     if (width == 0 && height == 0) return RT_DONE;
     if (width == 0 || height == 0) return RT_EBADARG;
@@ -519,7 +520,15 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height,
     if (o.order != RT_ORDER_EXACT && o.order != RT_ORDER_FAST) return RT_EBADARG;
     if (o.spp > RT_MAX_SPP) return RT_ETOOBIG;
     if (width > (1u << 20) || height > (1u << 20)) return RT_ETOOBIG;
-    int rc = rtl::check_scene(scene, n);
+    // The window (opts->win_*): from here on (width, height) is the raster this call renders and
+    // returns — slabs, bands, staging, levels and the scatter are sized on it — and only
+    // rt_launch_rows is handed the image's (img_w, img_h) and the origin.
+    rt_window win;
+    int rc = rt_opts_window(o, img_w, img_h, &win);
+    if (rc != RT_OK) return rc;
+    width = win.w;
+    height = win.h;
+    rc = rtl::check_scene(scene, n);
     if (rc != RT_OK) return rc;
     int navail = 0;
     if (hipGetDeviceCount(&navail) != hipSuccess || navail <= 0) return RT_ENODEV;
@@ -604,11 +613,13 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height,
             const uint32_t valid = valid_rows(s);
             for (uint32_t b = 0; b < nb && err == RT_OK; ++b) {
                 const uint32_t b0 = b * band, b1 = std::min(slab, b0 + band);
-                err = rt_launch_rows(c->p, width, height, depth, rb, s, ns, render_prec, o.order, o.spp, o.seed, b0,
-                                     b1, slab_ren, slab_lv, c->render, (o.flags & RT_LEVELS_HIT) ? 1 : 0);
-                if (err == RT_ENOMEM && trim_idle(dev) > 0) // (a failed grow launches nothing)
-                    err = rt_launch_rows(c->p, width, height, depth, rb, s, ns, render_prec, o.order, o.spp, o.seed,
-                                         b0, b1, slab_ren, slab_lv, c->render, (o.flags & RT_LEVELS_HIT) ? 1 : 0);
+                auto launch = [&] {
+                    return rt_launch_rows(c->p, img_w, img_h, depth, win.x0, win.y0, width, height, rb, s, ns, render_prec,
+                                          o.order, o.spp, o.seed, b0, b1, slab_ren, slab_lv, c->render,
+                                          (o.flags & RT_LEVELS_HIT) ? 1 : 0);
+                };
+                err = launch();
+                if (err == RT_ENOMEM && trim_idle(dev) > 0) err = launch(); // (a failed grow launches nothing)
                 // integer frame: the band's image rows quantised behind its render, before its event
                 if (err == RT_OK && integer && b0 < std::min(b1, valid))
                     err = rt_quantize(slab_ren + (size_t)b0 * rrow, RT_OUT_F64,

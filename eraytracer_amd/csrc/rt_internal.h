@@ -8,13 +8,33 @@
 
 #include "../../include/rt_mi355x.h"
 
-// rt_launch_spp restricted to slab rows [row_begin, min(row_end, slab rows)) (rt_render.hip).
-// row_begin must be a multiple of 16 (the tile height); d_out / d_levels point at slab row 0.
+// rt_launch_window restricted to slab rows [row_begin, min(row_end, slab rows)) of the window
+// (rt_render.hip): (width, height) is the image, (x0, y0, win_w, win_h) the window, on which the
+// slab, its rows and the buffers are sized.  row_begin must be a multiple of 16 (the tile height);
+// d_out / d_levels point at slab row 0.
 // levels_hit: d_levels gets the primary-hit mask (1 / 0) instead of the level count (RT_LEVELS_HIT).
-int rt_launch_rows(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t row_block,
-                   uint32_t shard, uint32_t nshards, int precision, int order, uint32_t spp, uint64_t seed,
-                   uint32_t row_begin, uint32_t row_end, void *d_out, uint8_t *d_levels, void *stream,
-                   int levels_hit = 0);
+int rt_launch_rows(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t x0, uint32_t y0,
+                   uint32_t win_w, uint32_t win_h, uint32_t row_block, uint32_t shard, uint32_t nshards, int precision,
+                   int order, uint32_t spp, uint64_t seed, uint32_t row_begin, uint32_t row_end, void *d_out,
+                   uint8_t *d_levels, void *stream, int levels_hit = 0);
+
+// The window an options block selects in a width x height image (o: the boundary's own copy, zero
+// past the caller's struct_size): win_w = win_h = 0 is the whole frame.  RT_EBADARG for exactly one
+// zero size, an origin with a zero size, or a window that leaves the image.  Calls nothing.
+struct rt_window {
+    uint32_t x0, y0, w, h;
+};
+inline int rt_opts_window(const rt_opts &o, uint32_t width, uint32_t height, rt_window *win) {
+    if (o.win_w == 0 && o.win_h == 0) {
+        if (o.win_x0 || o.win_y0) return RT_EBADARG;
+        *win = rt_window{0, 0, width, height};
+        return RT_OK;
+    }
+    if (o.win_w == 0 || o.win_h == 0) return RT_EBADARG;
+    if ((uint64_t)o.win_x0 + o.win_w > width || (uint64_t)o.win_y0 + o.win_h > height) return RT_EBADARG;
+    *win = rt_window{o.win_x0, o.win_y0, o.win_w, o.win_h};
+    return RT_OK;
+}
 
 // Replace the scene of a prepared context in place (its work space, streams and events are
 // kept; captured frame graphs are invalidated).  No launch of p may be in flight.

@@ -293,8 +293,9 @@ int rt_ppm_format(const void *d_rgb, int precision, uint32_t width, uint32_t hei
     return rc;
 }
 
-int rt_render_ppm_file(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height, uint32_t depth,
+int rt_render_ppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, uint32_t depth,
                        const rt_opts *opts, uint32_t max_value, const char *path, rt_stats *stats) {
+    uint32_t width = img_w, height = img_h; // the window's from the window check on: the file is the window's
     if (!path) return RT_EBADARG;
     if (width == 0 && height == 0) return RT_DONE;
     if (width == 0 || height == 0) return RT_EBADARG;
@@ -309,10 +310,14 @@ int rt_render_ppm_file(const rt_elem *scene, uint32_t n, uint32_t width, uint32_
     o.precision = RT_OUT_F64; // the reference's values: the text is byte-exact
     o.out_levels = nullptr;
     FILE *f = nullptr;
-    int rc = RT_OK;
+    rt_window win;
+    int rc = rt_opts_window(o, img_w, img_h, &win);
+    if (rc != RT_OK) return rc;
+    width = win.w;
+    height = win.h;
     if (o.ndev != 1) { // several devices: rt_render assembles the frame on the host
         std::vector<double> img((size_t)width * height * 3);
-        rc = rt_render(scene, n, width, height, depth, &o, img.data(), stats);
+        rc = rt_render(scene, n, img_w, img_h, depth, &o, img.data(), stats);
         if (rc != RT_OK) return rc;
         f = std::fopen(path, "wb");
         if (!f) return RT_EBADARG;
@@ -338,8 +343,8 @@ int rt_render_ppm_file(const rt_elem *scene, uint32_t n, uint32_t width, uint32_
     do {
         if ((rc = rt_ctx_device_buffer(ctx, 0, frame_bytes, &d_rgb)) != RT_OK) break;
         if ((rc = rt_ctx_device_buffer(ctx, 2, cap, &d_text)) != RT_OK) break;
-        rc = rt_launch_spp(rt_ctx_prepared(ctx), width, height, depth, o.row_block, 0, 1, RT_OUT_F64, o.order, o.spp,
-                           o.seed, d_rgb, nullptr, st);
+        rc = rt_launch_window(rt_ctx_prepared(ctx), img_w, img_h, depth, win.x0, win.y0, width, height, o.row_block, 0, 1,
+                              RT_OUT_F64, o.order, o.spp, o.seed, d_rgb, nullptr, st);
         if (rc != RT_OK) break;
         rc = rt_ppm_format(d_rgb, RT_OUT_F64, width, height, max_value, static_cast<char *>(d_text), cap, &len, st);
         if (rc == RT_ERANGE) { // a colour BEAM would print as a bignum: format on the host

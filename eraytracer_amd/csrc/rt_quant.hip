@@ -219,8 +219,9 @@ int rt_quantize(const void *d_rgb, int precision, uint64_t n_values, uint32_t ma
     return RT_OK;
 }
 
-int rt_render_rawppm_file(const rt_elem *scene, uint32_t n, uint32_t width, uint32_t height, uint32_t depth,
+int rt_render_rawppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, uint32_t depth,
                           const rt_opts *opts, uint32_t max_value, const char *path, rt_stats *stats) {
+    uint32_t width = img_w, height = img_h; // the window's from the window check on: the file is the window's
     if (!path) return RT_EBADARG;
     if (width == 0 && height == 0) return RT_DONE;
     if (width == 0 || height == 0) return RT_EBADARG;
@@ -235,6 +236,11 @@ int rt_render_rawppm_file(const rt_elem *scene, uint32_t n, uint32_t width, uint
     if (o.spp == 0) o.spp = 1;
     if (o.row_block == 0) o.row_block = 16;
     if (o.ndev == 0) o.ndev = 1;
+    rt_window win;
+    int rc = rt_opts_window(o, img_w, img_h, &win);
+    if (rc != RT_OK) return rc;
+    width = win.w;
+    height = win.h;
     const int fmt = max_value > 255 ? RT_OUT_U16 : RT_OUT_U8;
     const size_t osz = fmt == RT_OUT_U16 ? 2 : 1;
     const size_t nval = (size_t)width * height * 3;
@@ -242,12 +248,11 @@ int rt_render_rawppm_file(const rt_elem *scene, uint32_t n, uint32_t width, uint
     o.precision = fmt;
     o.max_value = max_value;
     o.out_levels = nullptr;
-    int rc = RT_OK;
     if (o.ndev != 1) { // several devices: rt_render assembles the integer frame on the host
         std::vector<unsigned char> img(nval * osz);
         rt_stats st;
         std::memset(&st, 0, sizeof st);
-        rc = rt_render(scene, n, width, height, depth, &o, img.data(), &st);
+        rc = rt_render(scene, n, img_w, img_h, depth, &o, img.data(), &st);
         if (rc != RT_OK) return rc;
         if (stats) *stats = st;
         if (st.flags & RT_STATS_CLAMPED) return RT_ERANGE; // P3 would print a negative number
@@ -271,8 +276,8 @@ int rt_render_rawppm_file(const rt_elem *scene, uint32_t n, uint32_t width, uint
         if ((rc = rt_ctx_clamped(ctx, &d_clamped)) != RT_OK) break;
         if ((rc = rt_ctx_host_buffer(ctx, nval * osz, &h_int)) != RT_OK) break;
         if (hipMemsetAsync(d_clamped, 0, sizeof clamped, st) != hipSuccess) { rc = RT_EHIP; break; }
-        rc = rt_launch_spp(rt_ctx_prepared(ctx), width, height, depth, o.row_block, 0, 1, RT_OUT_F64, o.order, o.spp,
-                           o.seed, d_rgb, nullptr, st);
+        rc = rt_launch_window(rt_ctx_prepared(ctx), img_w, img_h, depth, win.x0, win.y0, width, height, o.row_block, 0, 1,
+                              RT_OUT_F64, o.order, o.spp, o.seed, d_rgb, nullptr, st);
         if (rc != RT_OK) break;
         if ((rc = rt_quantize(d_rgb, RT_OUT_F64, nval, max_value, fmt, d_int, d_clamped, st)) != RT_OK) break;
         // the samples and the counter to pinned memory by DMA; the file is written from there

@@ -103,7 +103,7 @@ struct rt_prepared {
     T *buf(Work w) const {
         return static_cast<T *>(work[w].ptr);
     }
-    long long pmask_key[8] = {};
+    long long pmask_key[12] = {};
     bool pmask_valid = false;
     // the shadow pass runs on a second, low-priority stream beside the reflection chain
     // shading of level 0 and of the deeper levels.  The caller's stream plus these stay
@@ -133,8 +133,8 @@ struct rt_prepared {
     } kt[4];
     hipStream_t cap = nullptr;
     hipGraphExec_t gexec = nullptr;
-    long long gkey[12] = {};
-    long long last_key[12] = {};
+    long long gkey[16] = {};
+    long long last_key[16] = {};
     bool last_valid = false;
 };
 
@@ -299,8 +299,8 @@ auto with_sph(bool staged, bool sph_only, F &&f) {
 }
 
 template <int ORDER, int PREC, bool GENPOW>
-int launch_t(rt_prepared *p, int W, int H, int depth, int rb, int shard, int nshards, int row0, int row_end,
-             void *out, uint8_t *levels, hipStream_t st, int levels_hit) {
+int launch_t(rt_prepared *p, int W, int H, const ImageGeom &im, int depth, int rb, int shard, int nshards, int row0,
+             int row_end, void *out, uint8_t *levels, hipStream_t st, int levels_hit) {
     dim3 grid((W + TILE - 1) / TILE, (row_end - row0 + TILE - 1) / TILE);
     size_t lds = ORDER == RT_ORDER_EXACT ? (size_t)depth * BLOCK * 12 + (size_t)BLOCK * 24 : 0;
     KtScope kt(p, RT_KT_RENDER, st);
@@ -309,7 +309,7 @@ int launch_t(rt_prepared *p, int W, int H, int depth, int rb, int shard, int nsh
         with_bool(!p->hdr.beam_ok, [&](auto nb) {
             hipLaunchKernelGGL((k_render<ORDER, PREC, decltype(lv)::value, GENPOW, decltype(nb)::value>), grid,
                                dim3(BLOCK), lds, st, p->hdr, p->d_tab, p->d_itab, W, H, depth, rb, shard, nshards, row0,
-                               row_end, out, levels, levels_hit);
+                               row_end, out, levels, levels_hit, im.IW, im.IH, im.x0, im.y0);
         });
     });
     HIPCHK(hipGetLastError());
@@ -606,14 +606,17 @@ bool wave_single_write(const rt_prepared *p, int D, bool levels) {
 
 // acc (slab row 0, binary64, or null): supersampled passes fold their sample into it where each
 // pixel is written (put_pixel) — only valid when wave_single_write holds.
+// W x H is the raster the call renders (slabs, tiles, queues and stores are sized on it): a window
+// of the image `im`, the whole frame being {W, H, 0, 0}.
 template <int PREC, bool GENPOW>
-int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns, int row_begin, int row_end, void *out,
-                     uint8_t *levels, hipStream_t st, int spp = 1, int sample = 0, unsigned long long seed = 0,
-                     double *acc = nullptr, int levels_hit = 0) {
+int launch_wavefront(rt_prepared *p, int W, int H, const ImageGeom &im, int D, int rb, int sh, int ns, int row_begin,
+                     int row_end, void *out, uint8_t *levels, hipStream_t st, int spp = 1, int sample = 0,
+                     unsigned long long seed = 0, double *acc = nullptr, int levels_hit = 0) {
     // renders slab rows [row_begin, row_end) (row_begin a multiple of TILE); out / levels point at slab row 0.
     // levels_hit: k_primary writes the primary-hit mask (what it always writes: 1 on a hit, 0 on a
     // miss) and the later kernels do not count levels, so the fused path stays on
     uint8_t *const levels_primary = levels;
+    const SceneHdr &hdr = p->hdr;
     if (levels_hit) levels = nullptr;
     const int slab_rows = row_end - row_begin;
     const int nlev = D > 0 ? D : 1;
@@ -666,13 +669,14 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
     if (rc == RT_OK && overlap) rc = side_stream(p, D);
     if (rc != RT_OK) return rc;
     // the primary rays' candidate masks of the whole slab (k_pmask), recomputed only when the
-    // frame geometry or the scene changed (or after rt_trim)
+    // frame geometry — the raster's and the image's: two windows of one size at different origins
+    // see different rays — or the scene changed (or after rt_trim)
     const unsigned long long *pmask = nullptr;
     const unsigned short *pempty = nullptr; // after the masks: one byte per half-tile, 1 = every mask zero
     if (p->hdr.beam_ok && D > 0) {
         const int slab_all = (int)rt_shard_rows(H, rb, ns);
         const size_t nhalf = (size_t)tiles_x * ((slab_all + TILE - 1) / TILE) * 2;
-        const long long key[8] = {W, H, rb, sh, ns, spp > 1, (long long)p->scene_gen, slab_all};
+        const long long key[12] = {W, H, rb, sh, ns, spp > 1, (long long)p->scene_gen, slab_all, im.IW, im.IH, im.x0, im.y0};
         if (!(p->pmask_valid && std::memcmp(key, p->pmask_key, sizeof(key)) == 0)) {
             p->pmask_valid = false;
             // New masks (and perhaps a new buffer): a frame graph captured with the old ones holds
@@ -682,10 +686,11 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
             const dim3 pg((unsigned)std::min<size_t>(4096, (nhalf + 3) / 4));
             KtScope kt(p, RT_KT_PMASK, st);
             with_bool(spp > 1, [&](auto ss) {
-                hipLaunchKernelGGL(k_pmask<decltype(ss)::value>, pg, dim3(256), 0, st, p->hdr, p->d_tab, p->d_itab, W, H,
+                hipLaunchKernelGGL(k_pmask<decltype(ss)::value>, pg, dim3(256), 0, st, hdr, p->d_tab, p->d_itab, W, H,
                                    rb, sh, ns, slab_all, (int)nhalf, p->buf<unsigned long long>(rt_prepared::W_PMASK),
                                    reinterpret_cast<unsigned char *>(p->buf<unsigned long long>(rt_prepared::W_PMASK) +
-                                                           nhalf * p->hdr.n_chunk));
+                                                           nhalf * p->hdr.n_chunk),
+                                   im);
             });
             HIPCHK(hipGetLastError());
             std::memcpy(p->pmask_key, key, sizeof(key));
@@ -707,7 +712,7 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
     const size_t lds = staged ? (size_t)p->hdr.l_bytes : 0; // the SPH = 2 kernels' dynamic LDS; 0 for SPH < 2
     // Reflection kernels of levels that traverse the sphere BVH: after the staged tables in LDS,
     // the BVH nodes and sphere rows (when they fit BVH_LDS_MAX) and every lane's stack.
-    SceneHdr rhdr = p->hdr;
+    SceneHdr rhdr = hdr;
     size_t lds_bvh = lds;
     if (rhdr.bvh_ok) {
         const size_t nb = (size_t)rhdr.n_bvh * BVH_NODE_DOUBLES * 8, sb = (size_t)rhdr.n_sph * SPH_W * 8;
@@ -742,14 +747,14 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
         auto chk = [&](int k) { return d_child + (size_t)k * ntiles * TILE_SLOTS; };
         auto litk = [&](int k) { return d_lit + (size_t)k * ntiles * TILE_SLOTS; };
         const dim3 iblocks((ntiles + ITEMS_BLOCK - 1) / ITEMS_BLOCK);
-        const PassGeom g{W, H, rb, sh, ns, row0, spp, sample, seed, acc_p}; // level-0 records are rebuilt from it
+        const PassGeom g = make_pass_geom(W, im, rb, sh, ns, row0, spp, sample, seed, acc_p); // level-0 records are rebuilt from it
         const dim3 grid(std::min(ntiles, PRIMARY_GRID)); // k_primary: grid-stride loop over the tiles
         {
             KtScope kt(p, RT_KT_PRIMARY, st);
             with_bool(lv0 != nullptr, [&](auto has_lv) { // (without lv0 there is no lv either)
-                hipLaunchKernelGGL((k_primary<PREC, decltype(has_lv)::value>), grid, dim3(PRIMARY_BLOCK), 0, st, p->hdr,
-                                   p->d_tab, p->d_itab, W, H, D, rb, sh, ns, rows, row0, o, lv0, q, d_counts, ntiles, spp,
-                                   sample, seed, acc_p, pmask, pempty, nitems);
+                hipLaunchKernelGGL((k_primary<PREC, decltype(has_lv)::value>), grid, dim3(PRIMARY_BLOCK), 0, st, hdr,
+                                   p->d_tab, p->d_itab, W, im.y0 + H, D, rb, g.yoff, ns, rows, row0, o, lv0, q, d_counts, ntiles,
+                                   spp, sample, seed, acc_p, pmask, pempty, nitems, g.img);
             });
         }
         HIPCHK(hipGetLastError());
@@ -778,7 +783,7 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
             const int lblocks = k >= 2 ? std::min(sblocks, DEEP_LIGHT_BLOCKS) : sblocks;
             with_sph(staged, sph_only, [&](auto sph) {
                 hipLaunchKernelGGL((k_light<PREC, GENPOW, decltype(sph)::value>), dim3(lblocks), dim3(BLOCK), lds, ls(k),
-                                   p->hdr, p->d_tab, p->d_itab, k, o, qk(k), ik(k), nitems + k, colk(k), litk(k), g);
+                                   hdr, p->d_tab, p->d_itab, k, o, qk(k), ik(k), nitems + k, colk(k), litk(k), g);
             });
             HIPCHK(hipGetLastError());
             if (overlap) HIPCHK(hipEventRecord(p->ev_lit[k], ls(k)));
@@ -838,7 +843,7 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
                         auto launch = [&](auto deep_c, auto pad_c) {
                             hipLaunchKernelGGL((k_walk<PREC, GENPOW, decltype(sph)::value, decltype(bits_c)::value,
                                                        decltype(deep_c)::value, decltype(pad_c)::value>),
-                                               dim3(sblocksw), dim3(BLOCK), lds, s_, p->hdr, p->d_tab, p->d_itab, D, o, q,
+                                               dim3(sblocksw), dim3(BLOCK), lds, s_, hdr, p->d_tab, p->d_itab, D, o, q,
                                                ls_, lists, nitems, d_colbuf, d_child, d_lit, lo, hi, g);
                         };
                         // (PAD is launched with DEEP and BITS only; its instantiations without BITS
@@ -860,7 +865,7 @@ int launch_wavefront(rt_prepared *p, int W, int H, int D, int rb, int sh, int ns
             if (D > 2 && overlap) {
                 with_sph(staged, sph_only, [&](auto sph) {
                     hipLaunchKernelGGL((k_walk_deep<GENPOW, decltype(sph)::value>), dim3(sblocks), dim3(BLOCK), lds, st,
-                                       p->hdr, p->d_tab, p->d_itab, D, q, ls_, lists, nitems, d_child, colk(2));
+                                       hdr, p->d_tab, p->d_itab, D, q, ls_, lists, nitems, d_child, colk(2));
                 });
                 HIPCHK(hipGetLastError());
             }
@@ -892,14 +897,14 @@ bool graphs_on() {
 
 // Run enqueue(stream) for a frame: directly, or through the cached graph of identical frames.
 template <typename F>
-int launch_frame(rt_prepared *p, const long long (&args)[12], hipStream_t st, F &&enqueue) {
+int launch_frame(rt_prepared *p, const long long (&args)[16], hipStream_t st, F &&enqueue) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (!graphs_on() || hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
         return enqueue(st); // the caller is capturing (or graphs are off): plain launches
-    long long key[12];
+    long long key[16];
     std::memcpy(key, args, sizeof(key));
-    key[11] = (long long)p->gen; // a reallocated work space invalidates captured pointers
-    auto same = [&](const long long (&a)[12]) { return std::memcmp(a, key, sizeof(key)) == 0; };
+    key[15] = (long long)p->gen; // a reallocated work space invalidates captured pointers
+    auto same = [&](const long long (&a)[16]) { return std::memcmp(a, key, sizeof(key)) == 0; };
     if (p->gexec && same(p->gkey)) {
         HIPCHK(hipGraphLaunch(p->gexec, st));
         return RT_OK;
@@ -907,7 +912,7 @@ int launch_frame(rt_prepared *p, const long long (&args)[12], hipStream_t st, F 
     if (!(p->last_valid && same(p->last_key))) { // first time with these arguments: run directly
         const int rc = enqueue(st);
         std::memcpy(p->last_key, key, sizeof(key));
-        p->last_key[11] = (long long)p->gen;
+        p->last_key[15] = (long long)p->gen;
         p->last_valid = rc == RT_OK;
         return rc;
     }
@@ -917,7 +922,7 @@ int launch_frame(rt_prepared *p, const long long (&args)[12], hipStream_t st, F 
     const int rc = enqueue(p->cap);
     hipGraph_t gr = nullptr;
     const hipError_t e = hipStreamEndCapture(p->cap, &gr);
-    if (rc == RT_OK && e == hipSuccess && (long long)p->gen != key[11]) {
+    if (rc == RT_OK && e == hipSuccess && (long long)p->gen != key[15]) {
         // the work space or the primary masks changed while capturing: no device work was run —
         // drop the graph and render this frame directly.  The host state the capture changed is
         // reset first: primary masks computed during the capture were never written (their k_pmask
@@ -992,20 +997,29 @@ int rt_launch(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, u
 int rt_launch_spp(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t row_block,
                   uint32_t shard, uint32_t nshards, int precision, int order, uint32_t spp, uint64_t seed,
                   void *d_out, uint8_t *d_levels, void *stream) {
-    return rt_launch_rows(p, width, height, depth, row_block, shard, nshards, precision, order, spp, seed, 0, ~0u,
-                          d_out, d_levels, stream, 0);
+    return rt_launch_window(p, width, height, depth, 0, 0, width, height, row_block, shard, nshards, precision, order,
+                            spp, seed, d_out, d_levels, stream);
+}
+
+int rt_launch_window(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t x0, uint32_t y0,
+                     uint32_t win_w, uint32_t win_h, uint32_t row_block, uint32_t shard, uint32_t nshards, int precision,
+                     int order, uint32_t spp, uint64_t seed, void *d_out, uint8_t *d_levels, void *stream) {
+    return rt_launch_rows(p, width, height, depth, x0, y0, win_w, win_h, row_block, shard, nshards, precision, order, spp,
+                          seed, 0, ~0u, d_out, d_levels, stream, 0);
 }
 
 } // extern "C"
 
-// rt_launch_spp restricted to slab rows [row_begin, min(row_end, slab rows)): the boundary
-// (rt_host.hip) renders a frame in row bands so that each band's copy to the host overlaps
-// the next band's render.  row_begin must be a multiple of 16 (the tile height).
-int rt_launch_rows(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t row_block,
-                   uint32_t shard, uint32_t nshards, int precision, int order, uint32_t spp, uint64_t seed,
-                   uint32_t row_begin, uint32_t row_end, void *d_out, uint8_t *d_levels, void *stream, int levels_hit) {
+// rt_launch_window restricted to slab rows [row_begin, min(row_end, slab rows)) of the window: the
+// boundary (rt_host.hip) renders a frame in row bands so that each band's copy to the host overlaps
+// the next band's render.  row_begin must be a multiple of 16 (the tile height).  From here on
+// (W, H) is the raster the kernels tile and store — the window — and `im` the image it lies in.
+int rt_launch_rows(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t x0, uint32_t y0,
+                   uint32_t win_w, uint32_t win_h, uint32_t row_block, uint32_t shard, uint32_t nshards, int precision,
+                   int order, uint32_t spp, uint64_t seed, uint32_t row_begin, uint32_t row_end, void *d_out,
+                   uint8_t *d_levels, void *stream, int levels_hit) {
     if (!p || !d_out) return RT_EBADARG;
-    if (width == 0 && height == 0) return RT_DONE;
+    if (width == 0 && height == 0 && win_w == 0 && win_h == 0 && x0 == 0 && y0 == 0) return RT_DONE;
     if (width == 0 || height == 0) return RT_EBADARG;
     if (row_block == 0 || nshards == 0 || shard >= nshards) return RT_EBADARG;
     if (precision != RT_OUT_F64 && precision != RT_OUT_F32) return RT_EBADARG;
@@ -1013,14 +1027,18 @@ int rt_launch_rows(rt_prepared *p, uint32_t width, uint32_t height, uint32_t dep
     if (spp == 0) return RT_EBADARG;
     if (spp > RT_MAX_SPP) return RT_ETOOBIG;
     if (width > (1u << 20) || height > (1u << 20)) return RT_ETOOBIG;
-    uint32_t slab = rt_shard_rows(height, row_block, nshards);
+    // the window: not empty, inside the image (sums in 64 bits: x0 + win_w may pass 2^32)
+    if (win_w == 0 || win_h == 0) return RT_EBADARG;
+    if ((uint64_t)x0 + win_w > width || (uint64_t)y0 + win_h > height) return RT_EBADARG;
+    const ImageGeom im{(int)width, (int)height, (int)x0, (int)y0};
+    uint32_t slab = rt_shard_rows(win_h, row_block, nshards);
     if ((uint64_t)slab > 65535ull * TILE) return RT_ETOOBIG;
     if (row_begin % TILE) return RT_EBADARG;
     if (row_end > slab) row_end = slab;
     if (row_begin >= row_end) return RT_OK;
     DevGuard g(p->device);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int W = (int)width, H = (int)height, D = (int)depth, rb = (int)row_block, sh = (int)shard, ns = (int)nshards;
+    int W = (int)win_w, H = (int)win_h, D = (int)depth, rb = (int)row_block, sh = (int)shard, ns = (int)nshards;
     const int r0 = (int)row_begin, r1 = (int)row_end, slab_rows = (int)slab;
     if (spp > 1) { // RT_SUPERSAMPLING, on the wavefront engine: one pass per sample, summed in order
         // the slab rows inside the image (a prefix: global rows grow with slab rows)
@@ -1041,8 +1059,8 @@ int rt_launch_rows(rt_prepared *p, uint32_t width, uint32_t height, uint32_t dep
             const bool single = wave_single_write(p, D, lv != nullptr && !levels_hit);
             rc = with_prec_pow(single ? precision : RT_OUT_F64, p->hdr.int_pow, [&](auto prec, auto genpow) {
                 return launch_wavefront<decltype(prec)::value, decltype(genpow)::value>(
-                    p, W, H, D, rb, sh, ns, r0, r1, single ? d_out : smp, lv, st, (int)spp, s, seed, single ? acc : nullptr,
-                    levels_hit);
+                    p, W, H, im, D, rb, sh, ns, r0, r1, single ? d_out : smp, lv, st, (int)spp, s, seed,
+                    single ? acc : nullptr, levels_hit);
             });
             if (rc != RT_OK) return rc;
             if (single) continue;
@@ -1055,19 +1073,20 @@ int rt_launch_rows(rt_prepared *p, uint32_t width, uint32_t height, uint32_t dep
         return RT_OK;
     }
     if (!use_mega_engine(p, D, order)) { // the wavefront engine always evaluates the reference's exact order
-        const long long key[12] = {W, H, D, rb, sh, ns, precision, ((long long)r0 << 32) | r1,
-                                   (long long)(intptr_t)d_out, (long long)(intptr_t)d_levels, levels_hit, 0};
+        const long long key[16] = {W, H, D, rb, sh, ns, precision, ((long long)r0 << 32) | r1,
+                                   (long long)(intptr_t)d_out, (long long)(intptr_t)d_levels, levels_hit,
+                                   im.IW, im.IH, im.x0, im.y0, 0};
         return launch_frame(p, key, st, [&](hipStream_t s) {
             return with_prec_pow(precision, p->hdr.int_pow, [&](auto prec, auto genpow) {
                 return launch_wavefront<decltype(prec)::value, decltype(genpow)::value>(
-                    p, W, H, D, rb, sh, ns, r0, r1, d_out, d_levels, s, 1, 0, 0, nullptr, levels_hit);
+                    p, W, H, im, D, rb, sh, ns, r0, r1, d_out, d_levels, s, 1, 0, 0, nullptr, levels_hit);
             });
         });
     }
     return with_int<RT_ORDER_EXACT, RT_ORDER_FAST>(order, [&](auto ord) {
         return with_prec_pow(precision, p->hdr.int_pow, [&](auto prec, auto genpow) {
             return launch_t<decltype(ord)::value, decltype(prec)::value, decltype(genpow)::value>(
-                p, W, H, D, rb, sh, ns, r0, r1, d_out, d_levels, st, levels_hit);
+                p, W, H, im, D, rb, sh, ns, r0, r1, d_out, d_levels, st, levels_hit);
         });
     });
 }

@@ -44,14 +44,42 @@ struct Rec0 {
 };
 static_assert(sizeof(Rec0) == 16, "Rec0 is one 16-byte record");
 
-// Where a pass sits in the frame (what primary_dir needs besides the pixel).
+// The image a raster is a window of: the raster's pixel (x, row gy) is the image's (x0 + x, y0 + gy),
+// the image IW x IH pixels.  The whole frame is {W, H, 0, 0}.  Only primary_dir's callers read it:
+// tiles, queues, masks and stores work on the raster.
+struct ImageGeom {
+    int IW, IH, x0, y0;
+};
+
+// Where a pass sits in the frame (what primary_dir needs besides the pixel): the raster's width W,
+// its rows dealt to shards by raster row, and the image the raster is a window of.  The kernels that
+// rebuild level-0 rays hold these scalars across their record loops, where every one of them is
+// spilled to VGPR lanes, so the image's geometry is carried in as many registers as the raster's
+// height took before there were windows (nothing downstream of k_primary reads H: make_pass_geom):
+//   step  nshards * rb, yoff  y0 + shard * rb — raster row sr = qq * rb + rr is image row
+//         qq * step + rr + yoff (the shard interleave, then the window's first row)
+//   smp   (spp - 1) | sample << 12                        (spp <= RT_MAX_SPP = 4096)
+//   img   (IW - 1) | (IH - 1) << 20 | x0 << 40            (IW, IH <= 2^20, x0 < IW)
+// unpacked where they are used (opq: a few SALU instructions there, not hoisted).
 struct PassGeom {
-    int W, H, rb, shard, nshards, row0, spp, sample;
+    int W, rb, step, row0, yoff, smp;
+    unsigned long long img;
     unsigned long long seed;
     // RT_SUPERSAMPLING with one write per pixel and pass: the binary64 running sum of the
     // samples (at the pass's first row, like the output), or null — the pass writes `out` as is
     double *acc;
 };
+
+static_assert(RT_MAX_SPP <= (1 << 12), "PassGeom::smp holds spp - 1 and the sample in 12 bits each");
+__host__ __device__ inline PassGeom make_pass_geom(int W, const ImageGeom &im, int rb, int shard, int nshards, int row0,
+                                                   int spp, int sample, unsigned long long seed, double *acc) {
+    return PassGeom{W, rb, nshards * rb, row0, im.y0 + shard * rb, (spp - 1) | (sample << 12),
+                    (unsigned long long)(im.IW - 1) | ((unsigned long long)(im.IH - 1) << 20) |
+                        ((unsigned long long)im.x0 << 40),
+                    seed, acc};
+}
+__device__ __forceinline__ int geom_spp(const PassGeom &g) { return (opq(g.smp) & 0xFFF) + 1; }
+__device__ __forceinline__ int geom_sample(const PassGeom &g) { return opq(g.smp) >> 12; }
 
 constexpr int TILE_SLOTS = TILE * TILE;      // 256 records per tile and level
 constexpr int TILE_SHIFT = 8;                // slot -> tile
@@ -261,7 +289,7 @@ __device__ __forceinline__ void put_pixel(void *out, const PassGeom &g, size_t p
     }
     double *a = acc + pix * 3;
     D3 s = c;
-    const int sample = opq(g.sample), spp = opq(g.spp);
+    const int sample = geom_sample(g), spp = geom_spp(g);
     if (sample > 0) s = D3{a[0] + c.x, a[1] + c.y, a[2] + c.z};
     if (sample < spp - 1) {
         a[0] = s.x; a[1] = s.y; a[2] = s.z;
@@ -277,7 +305,7 @@ __device__ __forceinline__ void put_pixel(void *out, const PassGeom &g, size_t p
 // into -0.0, and so is each running sum) — the pass neither reads nor writes the pixel's 24 bytes.
 template <int PREC>
 __device__ __forceinline__ void put_background(void *out, const PassGeom &g, size_t pix) {
-    if (opq(g.acc) != nullptr && opq(g.sample) > 0 && opq(g.sample) < opq(g.spp) - 1) return;
+    if (opq(g.acc) != nullptr && geom_sample(g) > 0 && geom_sample(g) < geom_spp(g) - 1) return;
     put_pixel<PREC>(out, g, pix, D3{0.0, 0.0, 0.0});
 }
 
@@ -301,7 +329,8 @@ __global__ __launch_bounds__(256) void k_accum(size_t n, const double *__restric
     }
 }
 
-// The primary ray direction of pixel (x, image row gy): ray_through_pixel/3 (:510-511) at
+// The primary ray direction of pixel (x, image row gy) of the W x H image — image coordinates: the
+// callers add the raster's origin (ImageGeom, PassGeom) — ray_through_pixel/3 (:510-511) at
 // {X/Width, Y/Height} (:112), or the jittered sample position of RT_SUPERSAMPLING
 // (include/rt_mi355x.h).  Called by converged waves (normalize3 ballots).
 __device__ __forceinline__ D3 primary_dir(const SceneHdr &hdr, int W, int H, int spp, int sample,
@@ -331,6 +360,7 @@ __device__ __forceinline__ D3 primary_dir(const SceneHdr &hdr, int W, int H, int
 // the beam covers the four corners of every pixel: a jittered sample's screen point lies in its
 // pixel's rectangle, and the cone's section by the screen plane is an ellipse (convex), so every
 // sample ray of the block lies inside the beam.
+// (W, H, x, gy0, gy1: the image's, as primary_dir takes them)
 __device__ __forceinline__ Beam32 make_beam_corners32(const SceneHdr &h, int W, int H, int x, int gy0, bool a0,
                                                       int gy1, bool a1) {
     Beam32 b;
@@ -373,7 +403,8 @@ __device__ __forceinline__ Beam32 make_beam_corners32(const SceneHdr &h, int W, 
 template <bool JITTER>
 __global__ __launch_bounds__(256) void k_pmask(SceneHdr hdr, const double *__restrict__ tab, const int *__restrict__ itab,
                                                int W, int H, int rb, int shard, int nshards, int slab_rows, int nhalf,
-                                               unsigned long long *__restrict__ pm, unsigned char *__restrict__ pe) {
+                                               unsigned long long *__restrict__ pm, unsigned char *__restrict__ pe,
+                                               ImageGeom im) {
     const Scene S{hdr, tab, itab};
     const int lane = threadIdx.x & 63;
     const int tiles_x = (W + TILE - 1) / TILE;
@@ -388,9 +419,10 @@ __global__ __launch_bounds__(256) void k_pmask(SceneHdr hdr, const double *__res
         const bool a0 = x < W && lr0 < slab_rows && gy0 < H, a1 = x < W && lr1 < slab_rows && gy1 < H;
         Beam32 b;
         if (JITTER) {
-            b = make_beam_corners32(hdr, W, H, x, gy0, a0, gy1, a1);
+            b = make_beam_corners32(hdr, im.IW, im.IH, im.x0 + x, im.y0 + gy0, a0, im.y0 + gy1, a1);
         } else {
-            const D3 d0 = primary_dir(hdr, W, H, 1, 0, 0, x, gy0), d1 = primary_dir(hdr, W, H, 1, 0, 0, x, gy1);
+            const D3 d0 = primary_dir(hdr, im.IW, im.IH, 1, 0, 0, im.x0 + x, im.y0 + gy0),
+                     d1 = primary_dir(hdr, im.IW, im.IH, 1, 0, 0, im.x0 + x, im.y0 + gy1);
             b = make_beam_pair32(hdr, a0, d0, a1, d1);
         }
         unsigned long long any = 0;
@@ -411,8 +443,10 @@ __device__ __forceinline__ HitRec rec0_to_rec(const SceneHdr &hdr, const PassGeo
     const int x = r0.pix - lr * g.W;
     const int sr = g.row0 + lr; // slab row
     const int qq = idiv_dim(sr, g.rb);
-    const int gy = (qq * g.nshards + g.shard) * g.rb + (sr - qq * g.rb);
-    const D3 d = primary_dir(hdr, g.W, g.H, g.spp, g.sample, g.seed, x, gy);
+    const int iy = qq * g.step + (sr - qq * g.rb) + g.yoff; // image row
+    const unsigned long long img = opq(g.img);
+    const int IW = (int)((unsigned)img & 0xFFFFFu) + 1, IH = (int)((unsigned)(img >> 20) & 0xFFFFFu) + 1;
+    const D3 d = primary_dir(hdr, IW, IH, geom_spp(g), geom_sample(g), g.seed, (int)(img >> 40) + x, iy);
     HitRec r;
     r.hx = hdr.cam_x + d.x * r0.t; r.hy = hdr.cam_y + d.y * r0.t; r.hz = hdr.cam_z + d.z * r0.t;
     r.dx = d.x; r.dy = d.y; r.dz = d.z;
@@ -457,14 +491,17 @@ constexpr int PRIMARY_GRID = RT_PRIMARY_GRID;
 #endif
 template <int PREC, bool LEVELS>
 __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restrict__ tab,
-                                                           const int *__restrict__ itab, int W, int H, int depth,
-                                                           int rb, int shard, int nshards, int rows, int row0,
+                                                           const int *__restrict__ itab, int W, int Hend, int depth,
+                                                           int rb, int yoff, int nshards, int rows, int row0,
                                                            void *__restrict__ out, uint8_t *__restrict__ levels,
                                                            HitRec *__restrict__ q, int *__restrict__ cnt, int ntiles,
                                                            int spp, int sample, unsigned long long seed,
                                                            double *__restrict__ acc,
                                                            const unsigned long long *__restrict__ pmask,
-                                                           const unsigned short *__restrict__ pempty, int *__restrict__ nitems) {
+                                                           const unsigned short *__restrict__ pempty, int *__restrict__ nitems,
+                                                           unsigned long long img) {
+    // W: the raster's width; the image's geometry as PassGeom carries it (yoff, img; Hend = y0 + the
+    // raster's height: the first image row past the raster), in two scalars more than a whole frame took.
     // this pass covers slab rows [row0, row0 + rows); out/levels point at slab row row0; pmask (or
     // null): k_pmask's candidate masks over the whole slab, pempty its all-zero flags per tile (both halves')
     __shared__ int s_cnt[2][PRIMARY_BLOCK / 64]; // per tile, alternating (one barrier per tile)
@@ -476,7 +513,7 @@ __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restri
         for (int i = tid; i < LEVEL_COUNTS || i < depth; i += PRIMARY_BLOCK) nitems[i] = 0; // level_counts(depth)
     const D3 cam = {hdr.cam_x, hdr.cam_y, hdr.cam_z};
     const int tiles_x = (W + TILE - 1) / TILE;
-    const PassGeom geom{W, H, rb, shard, nshards, row0, spp, sample, seed, acc};
+    const PassGeom geom{W, rb, nshards * rb, row0, yoff, (spp - 1) | (sample << 12), img, seed, acc};
     // Sphere-only scenes with masks: a half-tile whose candidate masks are all zero has no ray that
     // can hit anything (the walk would visit nothing, and there is nothing else to scan), so its wave
     // traces none.  Without masks (brute force, no beams) and in mixed scenes no half-tile is empty.
@@ -496,7 +533,7 @@ __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restri
         flags_next = flags_of(tile + (int)gridDim.x);
         const int by = tile / tiles_x, bx = tile - by * tiles_x;
         const int x = bx * TILE + wave * 8 + (lane & 7);
-        // slab row -> image row through the shard interleave without a per-lane integer division:
+        // slab row -> image row (the shard interleave, then the window's first row) without a per-lane integer division:
         // the tile's first slab row is split once (wave-uniform), the lane's offset (< 16) added
         const int ly_base = row0 + by * TILE;
         const int q_base = ly_base / rb, r_base = ly_base - q_base * rb;
@@ -506,11 +543,11 @@ __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restri
                 rr -= rb;
                 ++qq;
             }
-            return (qq * nshards + shard) * rb + rr;
+            return qq * nshards * rb + rr + yoff;
         };
         // slab rows past the image (the last row block's tail) are never written: a
         // single-shard caller's buffer need only hold the image's rows
-        auto row_inside = [&](int lr) { return lr < rows && image_row(lr) < H; };
+        auto row_inside = [&](int lr) { return lr < rows && image_row(lr) < Hend; };
         const int lr0 = by * TILE + (lane >> 3), lr1 = lr0 + 8;
         // (the wave's entry at a wave-uniform address; both waves read both halves' flags)
         const int wv = __builtin_amdgcn_readfirstlane(wave); // (a scalar: what it selects stays wave-uniform)
@@ -559,10 +596,12 @@ __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restri
             continue;
         }
         auto pixel = [&](int lr, bool &inside, bool &active, D3 &d) {
-            const int gy = image_row(lr);
-            inside = x < W && lr < rows && gy < H;
+            const int iy = image_row(lr);
+            inside = x < W && lr < rows && iy < Hend;
             active = inside && depth > 0;
-            d = primary_dir(hdr, W, H, spp, sample, seed, x, gy);
+            const unsigned long long im = opq(img); // (unpacked here, not held across the tile loop)
+            const int IW = (int)((unsigned)im & 0xFFFFFu) + 1, IH = (int)((unsigned)(im >> 20) & 0xFFFFFu) + 1;
+            d = primary_dir(hdr, IW, IH, spp, sample, seed, (int)(im >> 40) + x, iy);
         };
         bool in0, in1, a0, a1;
         D3 d0, d1;

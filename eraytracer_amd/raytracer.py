@@ -57,10 +57,30 @@ def _max_value_ok(max_value):
         raise ValueError(f"badarg: MaxValue must be an integer in [1, 2^32), got {max_value!r}")
 
 
+def _window_ok(window, width, height):
+    """``window=(x0, y0, w, h)`` checked against the image (RT_WINDOW in include/rt_mi355x.h); None is
+    the whole frame.  Returns the four integers."""
+    if window is None:
+        return 0, 0, width, height
+    try:
+        x0, y0, w, h = window
+    except (TypeError, ValueError):
+        raise ValueError(f"badarg: window must be (x0, y0, w, h), got {window!r}") from None
+    for v in (x0, y0, w, h):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"badarg: window must hold integers, got {window!r}")
+    x0, y0, w, h = int(x0), int(y0), int(w), int(h)
+    if x0 < 0 or y0 < 0 or w < 1 or h < 1:
+        raise ValueError(f"badarg: window {window!r} is empty or has a negative origin")
+    if x0 + w > width or y0 + h > height:
+        raise ValueError(f"badarg: window {window!r} leaves the {width}x{height} image")
+    return x0, y0, w, h
+
+
 def render(width: int, height: int, scene=None, depth: int = 5, *, precision: str = "f64",
            order: str = "exact", ndev: int = 1, first_dev: int = 0, row_block: int = 16,
            levels: bool = False, stats: dict | None = None, spp: int = 1, seed: int = 0, out=None,
-           nshards: int = 0, max_value: int = 255):
+           nshards: int = 0, max_value: int = 255, window=None):
     """Render through ``rt_render`` and return a ``(height, width, 3)`` array (float64 or
     float32), plus the per-pixel levels array if ``levels``.  ``'done'`` for 0x0.
     ``precision="u8"`` / ``"u16"``: an integer frame (uint8 / uint16) quantised on the GPU,
@@ -73,26 +93,32 @@ def render(width: int, height: int, scene=None, depth: int = 5, *, precision: st
     include/rt_mi355x.h (not in the reference; levels then report sample 0).
     ``levels="hit"``: the levels array is the primary-hit mask (1 where the primary ray hits,
     RT_LEVELS_HIT) instead of the chain's level count — what the strategy funs need for the
-    reference's integer pixels, without turning the fused shading kernels off."""
+    reference's integer pixels, without turning the fused shading kernels off.
+    ``window=(x0, y0, w, h)``: render only that pixel window of the ``width`` x ``height`` image
+    (RT_WINDOW in include/rt_mi355x.h): the result is ``(h, w, 3)`` (levels ``(h, w)``), bit for
+    bit the crop ``[y0:y0+h, x0:x0+w]`` of the whole frame, and ``out`` must have that shape.  A
+    window that is empty or leaves the image raises ValueError before the library is called."""
     if not _sizes_ok(width, height):
         return DONE
     _depth_ok(depth)
-    if scene is None:
-        scene = default_scene()
-    elems = N.marshal(scene)
-    L = N.lib()
+    x0, y0, ww, wh = _window_ok(window, width, height)
     prec, dt = {"f64": (N.RT_OUT_F64, np.float64), "f32": (N.RT_OUT_F32, np.float32),
                 "u8": (N.RT_OUT_U8, np.uint8), "u16": (N.RT_OUT_U16, np.uint16)}[precision]
     _max_value_ok(max_value)
     if out is None:
-        out = np.empty((height, width, 3), dtype=dt)
-    elif out.shape != (height, width, 3) or out.dtype != dt or not out.flags.c_contiguous:
-        raise ValueError(f"out must be a C-contiguous {(height, width, 3)} {np.dtype(dt).name} array")
-    lv = np.empty((height, width), dtype=np.uint8) if levels else None
+        out = np.empty((wh, ww, 3), dtype=dt)
+    elif out.shape != (wh, ww, 3) or out.dtype != dt or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a C-contiguous {(wh, ww, 3)} {np.dtype(dt).name} array")
+    if scene is None:
+        scene = default_scene()
+    elems = N.marshal(scene)
+    L = N.lib()
+    lv = np.empty((wh, ww), dtype=np.uint8) if levels else None
     opts = N.RtOpts(ctypes.sizeof(N.RtOpts), first_dev, ndev, prec,
                     {"exact": N.RT_ORDER_EXACT, "fast": N.RT_ORDER_FAST}[order], row_block,
                     lv.ctypes.data if levels else None, spp, nshards, seed,
-                    N.RT_LEVELS_HIT if levels == "hit" else 0, max_value)
+                    N.RT_LEVELS_HIT if levels == "hit" else 0, max_value,
+                    *((x0, y0, ww, wh) if window is not None else (0, 0, 0, 0)))
     st = N.RtStats()
     rc = L.rt_render(elems, len(elems), width, height, depth, ctypes.byref(opts), out.ctypes.data, ctypes.byref(st))
     if rc == N.RT_DONE:
@@ -255,18 +281,22 @@ def raytrace(Width=4, Height=3, Filename="/tmp/traced.ppm", Recursion_depth=5, F
 
 
 def render_ppm_file(width: int, height: int, scene, depth: int, filename: str, *, max_value: int = 255,
-                    ndev: int = 1, first_dev: int = 0, spp: int = 1, seed: int = 0, binary: bool = False):
+                    ndev: int = 1, first_dev: int = 0, spp: int = 1, seed: int = 0, binary: bool = False,
+                    window=None):
     """Render and write the P3 file natively (rt_render_ppm_file): raytrace/5 + write_pixels_to_ppm/5.
     ``binary=True``: the P6 file of the same integers (rt_render_rawppm_file; see
     :func:`write_pixels_to_p6`); a frame with a negative value raises RtError (RT_ERANGE) and
-    no file is written."""
+    no file is written.  ``window=(x0, y0, w, h)``: the file is that window of the image, a
+    ``w`` x ``h`` file (see :func:`render`)."""
     if not _sizes_ok(width, height):
         return DONE
     _depth_ok(depth)
     if binary:
         _max_value_ok(max_value)
+    win = _window_ok(window, width, height) if window is not None else (0, 0, 0, 0)
     elems = N.marshal(scene)
-    opts = N.RtOpts(ctypes.sizeof(N.RtOpts), first_dev, ndev, N.RT_OUT_F64, N.RT_ORDER_EXACT, 16, None, spp, 0, seed)
+    opts = N.RtOpts(ctypes.sizeof(N.RtOpts), first_dev, ndev, N.RT_OUT_F64, N.RT_ORDER_EXACT, 16, None, spp, 0, seed,
+                    0, 0, *win)
     what = "rt_render_rawppm_file" if binary else "rt_render_ppm_file"
     rc = getattr(N.lib(), what)(elems, len(elems), width, height, depth, ctypes.byref(opts), max_value,
                                 str(filename).encode(), None)

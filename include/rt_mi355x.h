@@ -136,8 +136,41 @@ typedef struct rt_opts {
     /* appended after ABI 4's flags (additive: RT_ABI_VERSION stays 5) */
     uint32_t max_value;   /* RT_OUT_U8 / RT_OUT_U16: the samples' MaxValue; 0, or a struct_size that
                              ends before this field, selects 255 */
+    /* appended after max_value (additive: RT_ABI_VERSION stays 5) */
+    uint32_t win_x0, win_y0, win_w, win_h; /* RT_WINDOW: render only this pixel window of the width x height
+                             image.  win_w = win_h = 0, or a struct_size that ends before these fields,
+                             selects the whole frame.  RT_EBADARG for exactly one of win_w, win_h zero,
+                             for a non-zero origin with a zero size, and for a window that leaves the
+                             image; checked before the scene and before any HIP call */
 } rt_opts;
 #define RT_LEVELS_HIT 1
+
+/* RT_WINDOW — a pixel window of a frame, bit for bit the frame's crop.
+ * A window is (x0, y0, win_w, win_h) inside an image of width x height pixels:
+ *     win_w, win_h >= 1,  x0 + win_w <= width,  y0 + win_h <= height.
+ * Pixel values: window pixel (x, y) IS image pixel (x0+x, y0+y).  Its ray goes through
+ *     X = (x0+x)/width,  Y = (y0+y)/height,
+ * and with spp > 1 the RT_SUPERSAMPLING index is pixel = (y0+y)*width + (x0+x) in the whole image, so
+ * a window's samples are the whole frame's.  A pixel's bits do not depend on which wave traces it
+ * (the filters only skip objects that provably cannot be hit; the wave-uniform fast paths of pow,
+ * sqrt and division give the library's bits), so a window equals the crop [y0 : y0+win_h,
+ * x0 : x0+win_w] of the whole frame in every byte, colours and levels.
+ * Buffers: everything else about the call is that of a win_w x win_h frame.  The output is packed,
+ * win_h rows of win_w*3 elements; levels are win_w*win_h bytes; rows are dealt to shards by WINDOW
+ * row — row g of the window belongs to shard (g / row_block) % nshards — and a slab has
+ * rt_shard_rows(win_h, row_block, nshards) rows; rt_unshard and rt_slab_* are called with
+ * (win_w, win_h) and know nothing of windows.  x0 and y0 need no alignment (a window whose rows
+ * are multiples of 16 bytes gets wider stores where no sphere can be hit, the same bytes).
+ * Placing a packed window into a pitched whole frame is the caller's hipMemcpy2DAsync (source pitch
+ * win_w*3 elements, destination pitch width*3 elements, at row y0 and element x0*3): the library
+ * writes no pitched output.
+ * The window (0, 0, width, height) is the whole-frame call — one code path: rt_launch_spp is
+ * rt_launch_window with it, and rt_render without a window fills it in.
+ * rt_render with opts->win_*: width and height stay the image's, out_rgb and opts->out_levels are
+ * the window's (win_w*win_h*3 elements, win_w*win_h bytes), rt_stats.pixels = win_w*win_h; every
+ * other option (precision, integer frames, spp, nshards, ndev, RT_LEVELS_HIT, pinned or pageable
+ * destinations) works as for a win_w x win_h frame.  rt_render_ppm_file and rt_render_rawppm_file
+ * write a win_w x win_h file whose header says "win_w win_h". */
 
 /* RT_SUPERSAMPLING — stochastic supersampling (BASELINE.json config 5; the reference has
  * none, so this definition is the contract and the oracle restates it).  With spp > 1,
@@ -160,7 +193,7 @@ typedef struct rt_stats {
     double kernel_ms;   /* device time of the render kernels, and of an integer frame's quantise
                            passes between them (max over devices) */
     double total_ms;    /* wall time of the whole call, boundary to boundary */
-    uint64_t pixels;    /* W*H */
+    uint64_t pixels;    /* W*H; with a window win_w*win_h */
     int32_t ndev;       /* devices actually used */
     int32_t flags;      /* bit 0: out_rgb was pinned host memory (written by DMA directly);
                            bit 1 (RT_STATS_CLAMPED): an integer frame stored at least one channel as
@@ -278,6 +311,15 @@ int rt_launch(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth,
 int rt_launch_spp(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth,
                   uint32_t row_block, uint32_t shard, uint32_t nshards, int precision, int order,
                   uint32_t spp, uint64_t seed, void *d_out, uint8_t *d_levels, void *stream);
+/* rt_launch_spp for the window (x0, y0, win_w, win_h) of the width x height image (RT_WINDOW):
+ * d_out is the window's slab, rt_shard_rows(win_h, row_block, nshards) rows of win_w*3 elements,
+ * d_levels one byte per slab pixel.  RT_EBADARG for an empty window or one that leaves the image,
+ * RT_ETOOBIG as rt_launch_spp for a width or height above 2^20; the arguments are checked before
+ * any HIP call.  (The name holds no digits, see rt_render_rawppm_file.) */
+int rt_launch_window(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t x0, uint32_t y0,
+                     uint32_t win_w, uint32_t win_h, uint32_t row_block, uint32_t shard, uint32_t nshards,
+                     int precision, int order, uint32_t spp, uint64_t seed, void *d_out, uint8_t *d_levels,
+                     void *stream);
 /* Reassemble nshards gathered slabs (d_slabs = [nshards][shard_rows][W*3]) into the
  * row-major image d_image ([H][W*3]), on `stream`.  precision: the slabs' element, any of
  * RT_OUT_F64, RT_OUT_F32, RT_OUT_U8, RT_OUT_U16 (rows of W*3 elements of 8, 4, 1 or 2 bytes); the
