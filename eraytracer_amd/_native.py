@@ -30,6 +30,7 @@ RT_STATS_PINNED, RT_STATS_CLAMPED = 1, 2
 QUANT_V, QUANT_B, QUANT_MAX_BLOCKS = 8, 2048, 2048
 RT_ORDER_EXACT, RT_ORDER_FAST = 0, 1
 RT_MAX_SHARDS = 64
+RT_MAX_SPP = 4096
 RT_CFG_SIDE_STREAMS = 1
 RT_CFG_KERNEL_TIMING = 2
 RT_CFG_CULL = 3
@@ -43,7 +44,7 @@ RT_ENGINE_WAVE, RT_ENGINE_FUSED = 0, 1
 # every symbol include/rt_mi355x.h declares (tests/test_boundary.py checks the export list)
 EXPORTS = (
     "rt_abi_version", "rt_strerror", "rt_device_count", "rt_scene_check", "rt_scene_canon",
-    "rt_render", "rt_prepare", "rt_shard_rows", "rt_launch", "rt_launch_spp", "rt_launch_window", "rt_unshard", "rt_configure", "rt_release",
+    "rt_render", "rt_prepare", "rt_shard_rows", "rt_launch", "rt_launch_spp", "rt_launch_window", "rt_launch_samples", "rt_resolve", "rt_unshard", "rt_configure", "rt_release",
     "rt_update_scene",
     "rt_ppm_bound", "rt_ppm_format", "rt_render_ppm_file",
     "rt_quantize", "rt_render_rawppm_file",
@@ -148,6 +149,9 @@ def lib() -> ctypes.CDLL:
     L.rt_launch_spp.argtypes = [vp, u32, u32, u32, u32, u32, u32, i32, i32, u32, ctypes.c_uint64, vp, vp, vp]
     L.rt_launch_window.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, i32, i32, u32, ctypes.c_uint64,
                                    vp, vp, vp]
+    L.rt_launch_samples.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, ctypes.c_uint64, u32, u32,
+                                    vp, vp, vp]
+    L.rt_resolve.argtypes = [vp, ctypes.c_uint64, u32, i32, u32, vp, vp, vp]
     L.rt_ppm_bound.restype = ctypes.c_size_t
     L.rt_ppm_bound.argtypes = [u32, u32, u32]
     L.rt_ppm_format.argtypes = [vp, i32, u32, u32, u32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), vp]

@@ -14,11 +14,17 @@
 // workgroups and strides over the rest.  Up to 15 leading values (until the output is 16-byte
 // aligned) and up to 7 trailing ones are done one by one by the first workgroup; when the input
 // is not 16-byte aligned behind that head, the body loads element by element (same bytes).
+//
+// k_resolve (RT_PROGRESSIVE) is k_quant with a division in front and two more outputs: a binary64
+// sum of `samples` samples becomes the frame sum / samples, stored as binary64, as binary32 or
+// quantised by the rule above.  Same shape, same helpers; 24 B read per pixel and 24, 12, 3 or 6
+// written.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rt_mi355x.h"
@@ -104,6 +110,12 @@ __device__ inline void store8(uint16_t *p, const unsigned q[QUANT_V]) {
     *reinterpret_cast<uint4 *>(p) = w;
 }
 
+// the float outputs of k_resolve: one 16-byte piece, 2 binary64 or 4 binary32 values; p is 16-byte aligned
+__device__ inline void store_piece(double *p, const double v[2]) { *reinterpret_cast<double2 *>(p) = double2{v[0], v[1]}; }
+__device__ inline void store_piece(float *p, const double v[4]) {
+    *reinterpret_cast<float4 *>(p) = float4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+}
+
 // in/out: the whole array of n values; [head, head + nvec*QUANT_V) is the vector body, out + head
 // 16-byte aligned (and in + head too when VEC).  *clamped += the values stored as 0 because they
 // were negative or NaN: one atomic per wave that has any.
@@ -162,6 +174,105 @@ void launch_quant(const void *in, void *out, uint64_t n, uint32_t head, bool vec
                            static_cast<const TIN *>(in), static_cast<TOUT *>(out), n, head, nvec, maxv, maxi, clamped);
 }
 
+// One value of a resolved frame: the mean as TOUT, quantised when TOUT is an integer.
+template <typename TOUT>
+__device__ inline TOUT resolve1(double m, double maxv, unsigned maxi, bool *bad) {
+    if constexpr (std::is_floating_point<TOUT>::value)
+        return (TOUT)m;
+    else
+        return (TOUT)quant1(m, maxv, maxi, bad);
+}
+
+// k_quant's arrangement (head, nvec, VEC, clamped: see there) for out[i] = in[i] / cnt, the plain
+// binary64 division of k_accum and put_pixel, so that a resolved sum is the frame they write.
+// Integer outputs are k_quant's body: a lane converts 8 consecutive values (its one store needs them).
+// Float outputs deal the same 512 values of a wave to its lanes in 16-byte output pieces, so that each
+// load and store instruction of the wave covers contiguous memory (a lane's own 8 values would put its
+// four 16-byte stores 64 bytes apart).
+template <typename TOUT, bool VEC>
+__global__ __launch_bounds__(QUANT_BLOCK) void k_resolve(const double *__restrict__ in, TOUT *__restrict__ out,
+                                                         uint64_t n, uint32_t head, uint64_t nvec, double cnt, double maxv,
+                                                         unsigned maxi, unsigned long long *__restrict__ clamped) {
+    constexpr bool INT = !std::is_floating_point<TOUT>::value;
+    unsigned nbad = 0; // wave-uniform: every count below comes from a ballot
+    const double *bin = in + head;
+    TOUT *bout = out + head;
+    const uint64_t stride = (uint64_t)gridDim.x * QUANT_BLOCK;
+    const uint64_t wave0 = (uint64_t)blockIdx.x * QUANT_BLOCK + (threadIdx.x & ~63u);
+    for (uint64_t base = wave0; base < nvec; base += stride) { // wave-uniform trip count (the ballots)
+        if constexpr (!INT) {
+            constexpr unsigned CH = 16 / sizeof(TOUT); // values per piece
+            const uint64_t left = nvec - base;         // the wave's values: 8 per lane it would have had
+            const unsigned nval = (unsigned)(left < 64 ? left : 64) * QUANT_V;
+            const double *wi = bin + base * QUANT_V;
+            TOUT *wo = bout + base * QUANT_V;
+#pragma unroll
+            for (unsigned k = 0; k < QUANT_V / CH; ++k) {
+                const unsigned idx = (k * 64 + (threadIdx.x & 63u)) * CH;
+                if (idx < nval) { // (nval is a multiple of 8: a piece is inside or outside as a whole)
+                    double v[CH];
+                    if constexpr (VEC) {
+#pragma unroll
+                        for (unsigned j = 0; j < CH; j += 2) {
+                            const double2 a = *reinterpret_cast<const double2 *>(wi + idx + j);
+                            v[j] = a.x;
+                            v[j + 1] = a.y;
+                        }
+                    } else {
+#pragma unroll
+                        for (unsigned j = 0; j < CH; ++j) v[j] = wi[idx + j];
+                    }
+#pragma unroll
+                    for (unsigned j = 0; j < CH; ++j) v[j] = v[j] / cnt;
+                    store_piece(wo + idx, v);
+                }
+            }
+            continue;
+        }
+        const uint64_t c = base + (threadIdx.x & 63u);
+        unsigned badmask = 0;
+        if (c < nvec) {
+            double v[QUANT_V];
+            unsigned q[QUANT_V];
+            load8<double, VEC>(bin + c * QUANT_V, v);
+#pragma unroll
+            for (int k = 0; k < QUANT_V; ++k) {
+                bool bad = false;
+                q[k] = quant1(v[k] / cnt, maxv, maxi, &bad);
+                badmask |= (bad ? 1u : 0u) << k;
+            }
+            if constexpr (INT) store8(bout + c * QUANT_V, q);
+        }
+        if (__ballot(badmask != 0)) { // rare: count value by value
+#pragma unroll
+            for (int k = 0; k < QUANT_V; ++k) nbad += (unsigned)__popcll(__ballot((badmask >> k) & 1u));
+        }
+    }
+    if (blockIdx.x == 0) { // the scalar head and tail: fewer than 16 + 8 values
+        const uint64_t tail0 = (uint64_t)head + nvec * QUANT_V;
+        const uint64_t t = threadIdx.x;
+        const uint64_t i = t < head ? t : tail0 + (t - head); // threads [head, head + tail) take the tail
+        bool bad = false;
+        if (i < n) out[i] = resolve1<TOUT>(in[i] / cnt, maxv, maxi, &bad);
+        nbad += (unsigned)__popcll(__ballot(bad));
+    }
+    if (INT && nbad && clamped && (threadIdx.x & 63u) == 0) atomicAdd(clamped, (unsigned long long)nbad);
+}
+
+template <typename TOUT>
+void launch_resolve(const double *in, void *out, uint64_t n, uint32_t head, bool vec, double cnt, double maxv,
+                    unsigned maxi, unsigned long long *clamped, hipStream_t st) {
+    const uint64_t nvec = (n - head) / QUANT_V;
+    const uint64_t want = (nvec + QUANT_BLOCK - 1) / QUANT_BLOCK;
+    const unsigned grid = (unsigned)(want < 1 ? 1 : want > QUANT_MAX_BLOCKS ? QUANT_MAX_BLOCKS : want);
+    if (vec)
+        hipLaunchKernelGGL((k_resolve<TOUT, true>), dim3(grid), dim3(QUANT_BLOCK), 0, st, in, static_cast<TOUT *>(out), n,
+                           head, nvec, cnt, maxv, maxi, clamped);
+    else
+        hipLaunchKernelGGL((k_resolve<TOUT, false>), dim3(grid), dim3(QUANT_BLOCK), 0, st, in, static_cast<TOUT *>(out), n,
+                           head, nvec, cnt, maxv, maxi, clamped);
+}
+
 void p6_header(char h[64], uint32_t W, uint32_t H, uint32_t maxv) { std::snprintf(h, 64, "P6\n%u %u\n%u\n", W, H, maxv); }
 
 // the samples of a native-endian integer frame, 16-bit ones most significant byte first
@@ -215,6 +326,39 @@ int rt_quantize(const void *d_rgb, int precision, uint64_t n_values, uint32_t ma
         launch_quant<float, uint8_t>(d_rgb, d_out, n_values, (uint32_t)head, vec, maxv, max_value, cl, st);
     else
         launch_quant<float, uint16_t>(d_rgb, d_out, n_values, (uint32_t)head, vec, maxv, max_value, cl, st);
+    QCHK(hipGetLastError());
+    return RT_OK;
+}
+
+int rt_resolve(const double *d_sum, uint64_t n_values, uint32_t samples, int out_format, uint32_t max_value, void *d_out,
+               uint64_t *d_clamped, void *stream) {
+    if (!d_sum || !d_out) return RT_EBADARG;
+    if (out_format != RT_OUT_F64 && out_format != RT_OUT_F32 && out_format != RT_OUT_U8 && out_format != RT_OUT_U16)
+        return RT_EBADARG;
+    if (samples == 0) return RT_EBADARG;
+    if (samples > RT_MAX_SPP) return RT_ETOOBIG;
+    const bool integer = out_format == RT_OUT_U8 || out_format == RT_OUT_U16;
+    if (integer && max_value == 0) return RT_EBADARG;
+    if (integer && max_value > (out_format == RT_OUT_U8 ? 255u : (uint32_t)RT_MAX_INT_VALUE)) return RT_ETOOBIG;
+    const size_t osz = out_format == RT_OUT_F64 ? 8 : out_format == RT_OUT_F32 ? 4 : out_format == RT_OUT_U16 ? 2 : 1;
+    if ((uintptr_t)d_sum % 8 || (uintptr_t)d_out % osz || (uintptr_t)d_clamped % 8) return RT_EBADARG;
+    if (n_values == 0) return RT_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // the head: values before the output's first 16-byte boundary
+    uint64_t head = ((16 - (uintptr_t)d_out % 16) % 16) / osz;
+    if (head > n_values) head = n_values;
+    const bool vec = ((uintptr_t)d_sum + head * 8) % 16 == 0;
+    const double cnt = (double)samples, maxv = integer ? (double)max_value : 0.0;
+    const unsigned maxi = integer ? max_value : 0u;
+    unsigned long long *cl = reinterpret_cast<unsigned long long *>(d_clamped);
+    if (out_format == RT_OUT_F64)
+        launch_resolve<double>(d_sum, d_out, n_values, (uint32_t)head, vec, cnt, maxv, maxi, cl, st);
+    else if (out_format == RT_OUT_F32)
+        launch_resolve<float>(d_sum, d_out, n_values, (uint32_t)head, vec, cnt, maxv, maxi, cl, st);
+    else if (out_format == RT_OUT_U8)
+        launch_resolve<uint8_t>(d_sum, d_out, n_values, (uint32_t)head, vec, cnt, maxv, maxi, cl, st);
+    else
+        launch_resolve<uint16_t>(d_sum, d_out, n_values, (uint32_t)head, vec, cnt, maxv, maxi, cl, st);
     QCHK(hipGetLastError());
     return RT_OK;
 }

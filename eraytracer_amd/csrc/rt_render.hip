@@ -605,13 +605,14 @@ bool wave_single_write(const rt_prepared *p, int D, bool levels) {
 }
 
 // acc (slab row 0, binary64, or null): supersampled passes fold their sample into it where each
-// pixel is written (put_pixel) — only valid when wave_single_write holds.
+// pixel is written (put_pixel) — only valid when wave_single_write holds.  keep (RT_PROGRESSIVE):
+// such a pass only accumulates, whatever its sample — `out` is then never written.
 // W x H is the raster the call renders (slabs, tiles, queues and stores are sized on it): a window
 // of the image `im`, the whole frame being {W, H, 0, 0}.
 template <int PREC, bool GENPOW>
 int launch_wavefront(rt_prepared *p, int W, int H, const ImageGeom &im, int D, int rb, int sh, int ns, int row_begin,
                      int row_end, void *out, uint8_t *levels, hipStream_t st, int spp = 1, int sample = 0,
-                     unsigned long long seed = 0, double *acc = nullptr, int levels_hit = 0) {
+                     unsigned long long seed = 0, double *acc = nullptr, int levels_hit = 0, bool keep = false) {
     // renders slab rows [row_begin, row_end) (row_begin a multiple of TILE); out / levels point at slab row 0.
     // levels_hit: k_primary writes the primary-hit mask (what it always writes: 1 on a hit, 0 on a
     // miss) and the later kernels do not count levels, so the fused path stays on
@@ -747,14 +748,15 @@ int launch_wavefront(rt_prepared *p, int W, int H, const ImageGeom &im, int D, i
         auto chk = [&](int k) { return d_child + (size_t)k * ntiles * TILE_SLOTS; };
         auto litk = [&](int k) { return d_lit + (size_t)k * ntiles * TILE_SLOTS; };
         const dim3 iblocks((ntiles + ITEMS_BLOCK - 1) / ITEMS_BLOCK);
-        const PassGeom g = make_pass_geom(W, im, rb, sh, ns, row0, spp, sample, seed, acc_p); // level-0 records are rebuilt from it
+        const int smp = sample_arg(sample, keep);
+        const PassGeom g = make_pass_geom(W, im, rb, sh, ns, row0, spp, smp, seed, acc_p); // level-0 records are rebuilt from it
         const dim3 grid(std::min(ntiles, PRIMARY_GRID)); // k_primary: grid-stride loop over the tiles
         {
             KtScope kt(p, RT_KT_PRIMARY, st);
             with_bool(lv0 != nullptr, [&](auto has_lv) { // (without lv0 there is no lv either)
                 hipLaunchKernelGGL((k_primary<PREC, decltype(has_lv)::value>), grid, dim3(PRIMARY_BLOCK), 0, st, hdr,
                                    p->d_tab, p->d_itab, W, im.y0 + H, D, rb, g.yoff, ns, rows, row0, o, lv0, q, d_counts, ntiles,
-                                   spp, sample, seed, acc_p, pmask, pempty, nitems, g.img);
+                                   spp, smp, seed, acc_p, pmask, pempty, nitems, g.img);
             });
         }
         HIPCHK(hipGetLastError());
@@ -1010,15 +1012,12 @@ int rt_launch_window(rt_prepared *p, uint32_t width, uint32_t height, uint32_t d
 
 } // extern "C"
 
-// rt_launch_window restricted to slab rows [row_begin, min(row_end, slab rows)) of the window: the
-// boundary (rt_host.hip) renders a frame in row bands so that each band's copy to the host overlaps
-// the next band's render.  row_begin must be a multiple of 16 (the tile height).  From here on
-// (W, H) is the raster the kernels tile and store — the window — and `im` the image it lies in.
-int rt_launch_rows(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t x0, uint32_t y0,
-                   uint32_t win_w, uint32_t win_h, uint32_t row_block, uint32_t shard, uint32_t nshards, int precision,
-                   int order, uint32_t spp, uint64_t seed, uint32_t row_begin, uint32_t row_end, void *d_out,
-                   uint8_t *d_levels, void *stream, int levels_hit) {
-    if (!p || !d_out) return RT_EBADARG;
+namespace {
+
+// The size, shard and window checks of rt_launch_window and rt_launch_samples, in one place so that
+// they are the same: RT_OK, RT_DONE or an error; nothing is dereferenced and no HIP call is made.
+int launch_args_check(uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t win_w, uint32_t win_h,
+                      uint32_t row_block, uint32_t shard, uint32_t nshards, int precision, int order, uint32_t spp) {
     if (width == 0 && height == 0 && win_w == 0 && win_h == 0 && x0 == 0 && y0 == 0) return RT_DONE;
     if (width == 0 || height == 0) return RT_EBADARG;
     if (row_block == 0 || nshards == 0 || shard >= nshards) return RT_EBADARG;
@@ -1030,9 +1029,25 @@ int rt_launch_rows(rt_prepared *p, uint32_t width, uint32_t height, uint32_t dep
     // the window: not empty, inside the image (sums in 64 bits: x0 + win_w may pass 2^32)
     if (win_w == 0 || win_h == 0) return RT_EBADARG;
     if ((uint64_t)x0 + win_w > width || (uint64_t)y0 + win_h > height) return RT_EBADARG;
+    if ((uint64_t)rt_shard_rows(win_h, row_block, nshards) > 65535ull * TILE) return RT_ETOOBIG;
+    return RT_OK;
+}
+
+} // namespace
+
+// rt_launch_window restricted to slab rows [row_begin, min(row_end, slab rows)) of the window: the
+// boundary (rt_host.hip) renders a frame in row bands so that each band's copy to the host overlaps
+// the next band's render.  row_begin must be a multiple of 16 (the tile height).  From here on
+// (W, H) is the raster the kernels tile and store — the window — and `im` the image it lies in.
+int rt_launch_rows(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t x0, uint32_t y0,
+                   uint32_t win_w, uint32_t win_h, uint32_t row_block, uint32_t shard, uint32_t nshards, int precision,
+                   int order, uint32_t spp, uint64_t seed, uint32_t row_begin, uint32_t row_end, void *d_out,
+                   uint8_t *d_levels, void *stream, int levels_hit) {
+    if (!p || !d_out) return RT_EBADARG;
+    const int ok = launch_args_check(width, height, x0, y0, win_w, win_h, row_block, shard, nshards, precision, order, spp);
+    if (ok != RT_OK) return ok;
     const ImageGeom im{(int)width, (int)height, (int)x0, (int)y0};
     uint32_t slab = rt_shard_rows(win_h, row_block, nshards);
-    if ((uint64_t)slab > 65535ull * TILE) return RT_ETOOBIG;
     if (row_begin % TILE) return RT_EBADARG;
     if (row_end > slab) row_end = slab;
     if (row_begin >= row_end) return RT_OK;
@@ -1092,6 +1107,51 @@ int rt_launch_rows(rt_prepared *p, uint32_t width, uint32_t height, uint32_t dep
 }
 
 extern "C" {
+
+// RT_PROGRESSIVE: samples [sample_begin, sample_end) of rt_launch_window's frame folded into the
+// caller's binary64 sum, one wavefront pass per sample with rt_launch_rows' choice between the two
+// ways of summing.  Every pass has the keep bit: none divides, none writes a frame.
+int rt_launch_samples(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t x0, uint32_t y0,
+                      uint32_t win_w, uint32_t win_h, uint32_t row_block, uint32_t shard, uint32_t nshards, uint32_t spp,
+                      uint64_t seed, uint32_t sample_begin, uint32_t sample_end, double *d_sum, uint8_t *d_levels,
+                      void *stream) {
+    if (!p || !d_sum || (uintptr_t)d_sum % 8) return RT_EBADARG;
+    const int ok = launch_args_check(width, height, x0, y0, win_w, win_h, row_block, shard, nshards, RT_OUT_F64,
+                                     RT_ORDER_EXACT, spp);
+    if (ok != RT_OK) return ok;
+    if (sample_begin >= sample_end || sample_end > spp) return RT_EBADARG;
+    const ImageGeom im{(int)width, (int)height, (int)x0, (int)y0};
+    DevGuard g(p->device);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int W = (int)win_w, H = (int)win_h, D = (int)depth, rb = (int)row_block, sh = (int)shard, ns = (int)nshards;
+    const int slab_rows = (int)rt_shard_rows(win_h, row_block, nshards);
+    const size_t n = valid_slab_rows(H, rb, sh, ns) * W * 3; // the slab's elements inside the image, a prefix
+    if (n == 0) return RT_OK;
+    const int blocks = (int)std::min<size_t>(8192, (n + 255) / 256);
+    for (uint32_t s = sample_begin; s < sample_end; ++s) {
+        uint8_t *lv = s == 0 ? d_levels : nullptr;
+        const bool single = wave_single_write(p, D, lv != nullptr);
+        double *smp = nullptr; // the pass's own slab, where it does not write every pixel exactly once
+        if (!single) {
+            const int rc = grow(p, rt_prepared::W_SAMPLE, (size_t)slab_rows * W * 3 * sizeof(double));
+            if (rc != RT_OK) return rc;
+            smp = p->buf<double>(rt_prepared::W_SAMPLE);
+        }
+        // (a single-write pass is handed the sum as its frame too: with the keep bit it stores to neither)
+        const int rc = with_bool(!p->hdr.int_pow, [&](auto genpow) {
+            return launch_wavefront<RT_OUT_F64, decltype(genpow)::value>(p, W, H, im, D, rb, sh, ns, 0, slab_rows,
+                                                                         single ? d_sum : smp, lv, st, (int)spp, (int)s,
+                                                                         seed, single ? d_sum : nullptr, 0, true);
+        });
+        if (rc != RT_OK) return rc;
+        if (single) continue;
+        // k_accum told of a frame one sample longer: it folds and keeps the sum, and never reads `out`
+        hipLaunchKernelGGL(k_accum<RT_OUT_F64>, dim3(blocks), dim3(256), 0, st, n, smp, d_sum, nullptr, (int)s,
+                           (int)s + 2);
+        HIPCHK(hipGetLastError());
+    }
+    return RT_OK;
+}
 
 // Copy the blocks of one shard's slab to their rows in a row-major image.  dst_kind selects
 // hipMemcpyDeviceToDevice or DeviceToHost.

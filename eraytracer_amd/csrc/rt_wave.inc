@@ -58,7 +58,9 @@ struct ImageGeom {
 // height took before there were windows (nothing downstream of k_primary reads H: make_pass_geom):
 //   step  nshards * rb, yoff  y0 + shard * rb — raster row sr = qq * rb + rr is image row
 //         qq * step + rr + yoff (the shard interleave, then the window's first row)
-//   smp   (spp - 1) | sample << 12                        (spp <= RT_MAX_SPP = 4096)
+//   smp   (spp - 1) | keep << 12 | sample << 13            (spp <= RT_MAX_SPP = 4096)
+//         keep: RT_PROGRESSIVE, the pass only folds its sample into acc — what the last sample of
+//         a frame does differently (divide, write `out`) is never done
 //   img   (IW - 1) | (IH - 1) << 20 | x0 << 40            (IW, IH <= 2^20, x0 < IW)
 // unpacked where they are used (opq: a few SALU instructions there, not hoisted).
 struct PassGeom {
@@ -71,6 +73,8 @@ struct PassGeom {
 };
 
 static_assert(RT_MAX_SPP <= (1 << 12), "PassGeom::smp holds spp - 1 and the sample in 12 bits each");
+// The `sample` argument of make_pass_geom and k_primary: the sample's index above the keep bit.
+__host__ __device__ inline int sample_arg(int sample, bool keep) { return (sample << 1) | (keep ? 1 : 0); }
 __host__ __device__ inline PassGeom make_pass_geom(int W, const ImageGeom &im, int rb, int shard, int nshards, int row0,
                                                    int spp, int sample, unsigned long long seed, double *acc) {
     return PassGeom{W, rb, nshards * rb, row0, im.y0 + shard * rb, (spp - 1) | (sample << 12),
@@ -79,7 +83,8 @@ __host__ __device__ inline PassGeom make_pass_geom(int W, const ImageGeom &im, i
                     seed, acc};
 }
 __device__ __forceinline__ int geom_spp(const PassGeom &g) { return (opq(g.smp) & 0xFFF) + 1; }
-__device__ __forceinline__ int geom_sample(const PassGeom &g) { return opq(g.smp) >> 12; }
+__device__ __forceinline__ int geom_sample(const PassGeom &g) { return opq(g.smp) >> 13; }
+__device__ __forceinline__ bool geom_keep(const PassGeom &g) { return (opq(g.smp) & 0x1000) != 0; }
 
 constexpr int TILE_SLOTS = TILE * TILE;      // 256 records per tile and level
 constexpr int TILE_SHIFT = 8;                // slot -> tile
@@ -279,7 +284,8 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long z) {
 
 // A pixel's final colour for this pass.  Supersampled passes that write every pixel exactly once
 // (acc != null) fold the sample into the running sum right here, with k_accum's operations:
-// sum = acc + c (sample 0: c), kept in acc; the last sample writes sum / spp to the output.
+// sum = acc + c (sample 0: c), kept in acc; the last sample writes sum / spp to the output
+// (a pass with the keep bit is never the last: it keeps the sum, whatever its sample).
 template <int PREC>
 __device__ __forceinline__ void put_pixel(void *out, const PassGeom &g, size_t pix, const D3 &c) {
     double *const acc = opq(g.acc);
@@ -291,7 +297,7 @@ __device__ __forceinline__ void put_pixel(void *out, const PassGeom &g, size_t p
     D3 s = c;
     const int sample = geom_sample(g), spp = geom_spp(g);
     if (sample > 0) s = D3{a[0] + c.x, a[1] + c.y, a[2] + c.z};
-    if (sample < spp - 1) {
+    if (sample < spp - 1 || geom_keep(g)) {
         a[0] = s.x; a[1] = s.y; a[2] = s.z;
     } else {
         const double n = (double)spp;
@@ -300,12 +306,13 @@ __device__ __forceinline__ void put_pixel(void *out, const PassGeom &g, size_t p
 }
 
 // A background pixel (+0.0 in every channel: ?BACKGROUND_COLOUR, :82, or depth 0).  In the middle
-// samples of a supersampled frame its sum is left as it is: acc + (+0.0) == acc bit for bit, since
+// samples of a supersampled frame (with the keep bit: in every sample behind the first, sample 0
+// having stored the sum's +0.0) its sum is left as it is: acc + (+0.0) == acc bit for bit, since
 // acc is never -0.0 (each colour is a sum that starts from +0.0, which no rounded addition turns
 // into -0.0, and so is each running sum) — the pass neither reads nor writes the pixel's 24 bytes.
 template <int PREC>
 __device__ __forceinline__ void put_background(void *out, const PassGeom &g, size_t pix) {
-    if (opq(g.acc) != nullptr && geom_sample(g) > 0 && geom_sample(g) < geom_spp(g) - 1) return;
+    if (opq(g.acc) != nullptr && geom_sample(g) > 0 && (geom_sample(g) < geom_spp(g) - 1 || geom_keep(g))) return;
     put_pixel<PREC>(out, g, pix, D3{0.0, 0.0, 0.0});
 }
 
@@ -601,7 +608,8 @@ __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restri
             active = inside && depth > 0;
             const unsigned long long im = opq(img); // (unpacked here, not held across the tile loop)
             const int IW = (int)((unsigned)im & 0xFFFFFu) + 1, IH = (int)((unsigned)(im >> 20) & 0xFFFFFu) + 1;
-            d = primary_dir(hdr, IW, IH, spp, sample, seed, (int)(im >> 40) + x, iy);
+            // (sample is a sample_arg: its index unpacked here, not held across the tile loop)
+            d = primary_dir(hdr, IW, IH, spp, opq(sample) >> 1, seed, (int)(im >> 40) + x, iy);
         };
         bool in0, in1, a0, a1;
         D3 d0, d1;

@@ -130,6 +130,36 @@ def render(width: int, height: int, scene=None, depth: int = 5, *, precision: st
     return (out, lv) if levels else out
 
 
+def render_progressive(width: int, height: int, scene=None, depth: int = 5, *, spp: int, seed: int = 0, steps=1,
+                       precision: str = "f64", max_value: int = 255, window=None):
+    """A supersampled frame a few samples at a time (RT_PROGRESSIVE in include/rt_mi355x.h): an
+    iterator of ``(samples_done, array)``, one item per batch of samples, the array the preview of
+    the samples so far, ``(height, width, 3)`` (the window's shape with ``window``) in ``precision``.
+    ``steps``: the batch size, or a sequence of batch sizes (``progressive.batch_ends``).  The last
+    item's array is ``render(width, height, scene, depth, spp=spp, seed=seed, precision=precision,
+    max_value=max_value, window=window)`` in every byte.  The sum stays on the device
+    (``progressive.ProgressiveFrame``); every item is a copy to the host.  Bad arguments raise
+    ValueError here, before the library is loaded and before the first item is asked for."""
+    from . import progressive
+    if not _sizes_ok(width, height):
+        raise ValueError("function_clause: Width > 0, Height > 0 required (raytracer.erl:88-89)")
+    _depth_ok(depth)
+    ends = progressive.batch_ends(spp, steps)
+    progressive.seed_ok(seed)
+    progressive.format_ok(precision, max_value)
+    _window_ok(window, width, height)
+    if scene is None:
+        scene = default_scene()
+    N.marshal(scene)
+
+    def frames():
+        with progressive.ProgressiveFrame(scene, width, height, depth, spp=spp, seed=seed, window=window) as pf:
+            for end in ends:
+                pf.add(end - pf.samples_done)
+                yield end, pf.resolve(precision, max_value).cpu().numpy()
+    return frames()
+
+
 def _has_lights(scene) -> bool:
     from .records import tag
     return any(tag(t) == "point_light" for t in scene)

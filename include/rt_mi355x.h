@@ -189,6 +189,42 @@ typedef struct rt_opts {
  * so it is at depth 1. */
 #define RT_MAX_SPP 4096
 
+/* RT_PROGRESSIVE — a range of a frame's samples, bit for bit a prefix of the frame's sum, at the
+ * cost of the range; and a frame from a sum.
+ * The supersampled frame is fixed as (c_0 + ... + c_{spp-1}) / spp, summed left to right in binary64,
+ * and sample s of a pixel depends only on (seed, pixel, spp, s): a sum that is kept can be continued.
+ * rt_launch_samples folds samples [sample_begin, sample_end) of the spp-sample frame that
+ * rt_launch_window renders with the same (width, height, depth, window, row_block, shard, nshards,
+ * spp, seed) into the caller's sum; rt_resolve turns a sum into a frame of any RT_OUT_* format.
+ * The sum: d_sum is a caller-owned binary64 slab laid out like an RT_OUT_F64 output slab,
+ *   rt_shard_rows(win_h, row_block, nshards) rows of win_w*3 doubles; slab rows past the image are not
+ *   touched.  Sample 0 STORES (the caller need not clear d_sum, and a call with sample_begin = 0
+ *   restarts the frame); every later sample s does sum = sum + c_s in binary64, in sample order, so
+ *   after the call d_sum holds c_0 + ... + c_{sample_end-1} summed left to right — also when
+ *   sample_end = spp: no call divides, no call writes a frame.  (A background pixel's sum is +0.0
+ *   from sample 0 on and is neither read nor written by a later sample: a running sum is never -0.0,
+ *   so adding the background's +0.0 would give back its bits.)  The caller promises that d_sum holds
+ *   samples [0, sample_begin) of the same frame, which the library cannot check.  The call owns d_sum
+ *   until its stream reaches the end of the call; it is asynchronous on `stream` like rt_launch.
+ * The order is always the reference's (RT_ORDER_EXACT; rt_launch_spp ignores `order` for spp > 1 too).
+ *   spp = 1 is allowed: the one sample is the unjittered frame, rendered by the wavefront engine.
+ * d_levels (optional) is written by the call that holds sample 0, with sample 0's level counts
+ *   (RT_SUPERSAMPLING); a call with sample_begin > 0 leaves it untouched, so a caller may pass the
+ *   same arguments every time.
+ * Guarantees:
+ *   G1  Any partition gives the frame.  For any 0 = b_0 < b_1 < ... < b_k = spp, the calls for
+ *       [b_j, b_{j+1}) in order on one stream followed by rt_resolve(samples = spp) to RT_OUT_F64 or
+ *       RT_OUT_F32 give the slab rt_launch_window writes for the same arguments with RT_ORDER_EXACT,
+ *       in every byte, and the same levels — for every context configuration (side streams on or off,
+ *       culling on or off, levels requested or not).
+ *   G2  The sum does not depend on the partition: the sum after [0, k) is bit-equal whether one call
+ *       made it or several.
+ *   G3  An 8- or 16-bit preview is the quantised float preview: rt_resolve to RT_OUT_U8 / RT_OUT_U16
+ *       gives the bytes and the clamped count of rt_quantize applied to rt_resolve(..., RT_OUT_F64),
+ *       for 3 or 6 bytes per pixel of traffic out instead of 24.
+ *   G4  A call costs its samples: sample_end - sample_begin sample passes, nothing proportional to spp.
+ * Splitting a frame's samples over devices is not offered: the left-to-right sum forbids it. */
+
 typedef struct rt_stats {
     double kernel_ms;   /* device time of the render kernels, and of an integer frame's quantise
                            passes between them (max over devices) */
@@ -320,6 +356,31 @@ int rt_launch_window(rt_prepared *p, uint32_t width, uint32_t height, uint32_t d
                      uint32_t win_w, uint32_t win_h, uint32_t row_block, uint32_t shard, uint32_t nshards,
                      int precision, int order, uint32_t spp, uint64_t seed, void *d_out, uint8_t *d_levels,
                      void *stream);
+/* RT_PROGRESSIVE: fold samples [sample_begin, sample_end) of rt_launch_window's spp-sample frame into
+ * d_sum (see the contract above); writes no frame.  All checked before any HIP call and before p is
+ * read: RT_EBADARG for a null p or d_sum, a d_sum that is not 8-byte aligned, spp = 0,
+ * sample_begin >= sample_end or sample_end > spp; RT_ETOOBIG for spp > RT_MAX_SPP; the window, shard
+ * and size errors exactly as rt_launch_window. */
+int rt_launch_samples(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth,
+                      uint32_t x0, uint32_t y0, uint32_t win_w, uint32_t win_h,
+                      uint32_t row_block, uint32_t shard, uint32_t nshards,
+                      uint32_t spp, uint64_t seed, uint32_t sample_begin, uint32_t sample_end,
+                      double *d_sum, uint8_t *d_levels, void *stream);
+/* RT_PROGRESSIVE: a frame from a sum, asynchronously on `stream`; neither synchronises nor allocates.
+ *     m = d_sum[i] / (double)samples        (binary64, i < n_values)
+ *   RT_OUT_F64 stores m, RT_OUT_F32 (float)m, RT_OUT_U8 / RT_OUT_U16 min(trunc(m*max_value), max_value)
+ *   by rt_quantize's rule in every detail: a negative result or a NaN is stored as 0 and counted into
+ *   *d_clamped (optional, device memory, zeroed by the caller), -0.0 and values in (-1/max_value, 0)
+ *   give 0 uncounted, +inf gives max_value.  The array is flat, as for rt_quantize: pass the slab's
+ *   rows inside the image (a prefix).  The buffers must not overlap.
+ *   samples in [1, RT_MAX_SPP]: 0 is RT_EBADARG, more RT_ETOOBIG.  max_value is read for the integer
+ *   formats only: 0 is RT_EBADARG, above the format's limit RT_ETOOBIG.  Alignment: d_sum to 8 bytes,
+ *   d_out to its element, d_clamped to 8, anything else is RT_EBADARG; values before d_out's first
+ *   16-byte boundary and the last few are converted one by one, the rest eight per work-item (16-byte
+ *   loads when d_sum is 16-byte aligned there; the same bytes otherwise).  RT_EBADARG for a null
+ *   d_sum or d_out or a bad out_format; n_values 0 launches nothing.  All checked before any HIP call. */
+int rt_resolve(const double *d_sum, uint64_t n_values, uint32_t samples, int out_format,
+               uint32_t max_value, void *d_out, uint64_t *d_clamped, void *stream);
 /* Reassemble nshards gathered slabs (d_slabs = [nshards][shard_rows][W*3]) into the
  * row-major image d_image ([H][W*3]), on `stream`.  precision: the slabs' element, any of
  * RT_OUT_F64, RT_OUT_F32, RT_OUT_U8, RT_OUT_U16 (rows of W*3 elements of 8, 4, 1 or 2 bytes); the
