@@ -100,9 +100,7 @@ std::vector<rt_ctx *> &pool() {
 }
 
 void destroy_ctx(rt_ctx *c) {
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(c->device);
+    DevGuard g(c->device);
     if (c->p) rt_release(c->p);
     for (void *b : c->d_buf)
         if (b) (void)hipFree(b);
@@ -117,7 +115,6 @@ void destroy_ctx(rt_ctx *c) {
     if (c->render) (void)hipStreamDestroy(c->render);
     if (c->copy) (void)hipStreamDestroy(c->copy);
     if (c->copy2) (void)hipStreamDestroy(c->copy2);
-    if (prev >= 0) (void)hipSetDevice(prev);
     delete c;
 }
 
@@ -125,10 +122,8 @@ int create_ctx(int device, rt_ctx **out) {
     rt_ctx *c = new (std::nothrow) rt_ctx();
     if (!c) return RT_ENOMEM;
     c->device = device;
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    int rc = RT_OK;
-    if (hipSetDevice(device) != hipSuccess) rc = RT_ENODEV;
+    DevGuard g(device);
+    int rc = g.ok ? RT_OK : RT_ENODEV;
     if (rc == RT_OK && (hipStreamCreateWithFlags(&c->render, hipStreamNonBlocking) != hipSuccess ||
                         hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking) != hipSuccess ||
                         hipStreamCreateWithFlags(&c->copy2, hipStreamNonBlocking) != hipSuccess ||
@@ -138,7 +133,6 @@ int create_ctx(int device, rt_ctx **out) {
         if (hipEventCreateWithFlags(&c->band[i], hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&c->copied[i], hipEventDisableTiming) != hipSuccess)
             rc = RT_EHIP;
-    if (prev >= 0) (void)hipSetDevice(prev);
     if (rc != RT_OK) {
         destroy_ctx(c);
         return rc;
@@ -149,13 +143,11 @@ int create_ctx(int device, rt_ctx **out) {
 
 // The pinned staging ring's copy-out: rows [0, rows) of `src` (slab rows b0.., row pitch
 // rowbytes) to their image rows in `dst` through the shard interleave, split over host threads.
-void host_scatter(const char *src, uint32_t b0, uint32_t rows, uint32_t rowbytes, uint32_t H, uint32_t rb,
-                  uint32_t shard, uint32_t ns, char *dst) {
+void host_scatter(const char *src, uint32_t b0, uint32_t rows, uint32_t rowbytes, const rt_shard_map &m, char *dst) {
     auto body = [=](uint32_t lo, uint32_t hi) {
         for (uint32_t i = lo; i < hi; ++i) {
-            const uint64_t r = (uint64_t)b0 + i;
-            const uint64_t g = (r / rb * ns + shard) * rb + r % rb;
-            if (g < H) std::memcpy(dst + g * rowbytes, src + (uint64_t)i * rowbytes, rowbytes);
+            const uint64_t g = rt_shard_image_row(m, (uint64_t)b0 + i);
+            if (g < m.height) std::memcpy(dst + g * rowbytes, src + (uint64_t)i * rowbytes, rowbytes);
         }
     };
     const uint64_t bytes = (uint64_t)rows * rowbytes;
@@ -169,40 +161,6 @@ void host_scatter(const char *src, uint32_t b0, uint32_t rows, uint32_t rowbytes
     for (unsigned t = 1; t < nt && t * per < rows; ++t) th.emplace_back(body, t * per, std::min(rows, (t + 1) * per));
     body(0, std::min(rows, per));
     for (std::thread &x : th) x.join();
-}
-
-// Async copy of slab rows [b0, b1) of shard `shard` (device slab, row pitch rowbytes) to their
-// rows of the row-major host image (pinned), on `st`.  Row-block runs become 2D copies.
-int scatter_rows_async(const char *slab, uint32_t b0, uint32_t b1, uint32_t rowbytes, uint32_t H, uint32_t rb,
-                       uint32_t shard, uint32_t ns, char *image, hipStream_t st) {
-    uint32_t r = b0;
-    while (r < b1) {
-        const uint32_t q = r / rb, rr = r % rb;
-        const uint64_t g = ((uint64_t)q * ns + shard) * rb + rr;
-        if (g >= H) break; // later slab rows map further down: all past the image
-        if (rr == 0 && ns > 1) {
-            // whole row blocks inside [r, b1) and inside the image: one strided copy
-            uint32_t nblk = (b1 - r) / rb;
-            while (nblk > 0 && (((uint64_t)(q + nblk - 1) * ns + shard) * rb + rb) > H) --nblk;
-            if (nblk > 0) {
-                const size_t w = (size_t)rb * rowbytes;
-                if (hipMemcpy2DAsync(image + g * rowbytes, w * ns, slab + (uint64_t)r * rowbytes, w, w, nblk,
-                                     hipMemcpyDeviceToHost, st) != hipSuccess)
-                    return RT_EHIP;
-                r += nblk * rb;
-                continue;
-            }
-        }
-        // the rest of this row block (contiguous in both), clipped to the image and the band
-        uint32_t n = std::min(b1 - r, rb - rr);
-        if (ns == 1) n = b1 - r; // one shard: slab rows are image rows
-        n = (uint32_t)std::min<uint64_t>(n, H - g);
-        if (hipMemcpyAsync(image + g * rowbytes, slab + (uint64_t)r * rowbytes, (size_t)n * rowbytes,
-                           hipMemcpyDeviceToHost, st) != hipSuccess)
-            return RT_EHIP;
-        r += n;
-    }
-    return RT_OK;
 }
 
 bool is_pinned(const void *p, size_t bytes) {
@@ -229,6 +187,30 @@ uint32_t lcm_u(uint32_t a, uint32_t b) {
 }
 
 } // namespace
+
+// Slab rows [b0, b1) of shard m to their image rows (rt_internal.h).  The rows inside the image are
+// a prefix of the slab, so the copies stop at the shard's valid rows.
+int rt_scatter_rows_async(const char *slab, uint32_t b0, uint32_t b1, uint32_t rowbytes, const rt_shard_map &m,
+                          char *image, hipMemcpyKind kind, hipStream_t st) {
+    const uint32_t rb = m.row_block, ns = m.nshards, end = std::min(b1, rt_shard_valid_rows(m));
+    for (uint32_t r = b0; r < end;) {
+        char *dst = image + rt_shard_image_row(m, r) * rowbytes;
+        const char *src = slab + (uint64_t)r * rowbytes;
+        // whole row blocks inside [r, end): one strided copy
+        const uint32_t nblk = ns > 1 && r % rb == 0 ? (end - r) / rb : 0;
+        if (nblk > 0) {
+            const size_t w = (size_t)rb * rowbytes;
+            if (hipMemcpy2DAsync(dst, w * ns, src, w, w, nblk, kind, st) != hipSuccess) return RT_EHIP;
+            r += nblk * rb;
+            continue;
+        }
+        // the rest of this row block (contiguous in both); one shard: slab rows are image rows
+        const uint32_t n = ns == 1 ? end - r : std::min(end - r, rb - r % rb);
+        if (hipMemcpyAsync(dst, src, (size_t)n * rowbytes, kind, st) != hipSuccess) return RT_EHIP;
+        r += n;
+    }
+    return RT_OK;
+}
 
 int rt_ctx_acquire(int device, const rt_elem *scene, uint32_t n, rt_ctx **out) {
     *out = nullptr;
@@ -299,9 +281,7 @@ hipStream_t rt_ctx_stream(rt_ctx *c) { return c->render; }
 int rt_ctx_device_buffer(rt_ctx *c, int which, size_t bytes, void **out) {
     if (which < 0 || which > 2) return RT_EBADARG;
     if (c->d_cap[which] < bytes) {
-        int prev = -1;
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(c->device);
+        DevGuard g(c->device);
         if (c->d_buf[which]) {
             (void)hipStreamSynchronize(c->render);
             (void)hipStreamSynchronize(c->copy);
@@ -310,9 +290,7 @@ int rt_ctx_device_buffer(rt_ctx *c, int which, size_t bytes, void **out) {
         }
         c->d_buf[which] = nullptr;
         c->d_cap[which] = 0;
-        const hipError_t e = hipMalloc(&c->d_buf[which], bytes);
-        if (prev >= 0) (void)hipSetDevice(prev);
-        if (e != hipSuccess) {
+        if (hipMalloc(&c->d_buf[which], bytes) != hipSuccess) {
             c->d_buf[which] = nullptr;
             return RT_ENOMEM;
         }
@@ -324,12 +302,8 @@ int rt_ctx_device_buffer(rt_ctx *c, int which, size_t bytes, void **out) {
 
 int rt_ctx_clamped(rt_ctx *c, uint64_t **out) {
     if (!c->d_clamped) {
-        int prev = -1;
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(c->device);
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&c->d_clamped), sizeof(uint64_t));
-        if (prev >= 0) (void)hipSetDevice(prev);
-        if (e != hipSuccess) {
+        DevGuard g(c->device);
+        if (hipMalloc(reinterpret_cast<void **>(&c->d_clamped), sizeof(uint64_t)) != hipSuccess) {
             c->d_clamped = nullptr;
             return RT_ENOMEM;
         }
@@ -442,9 +416,7 @@ static size_t trim_idle(int device) {
     }
     size_t freed = 0;
     for (rt_ctx *c : idle) {
-        int prev = -1;
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(c->device);
+        DevGuard g(c->device);
         (void)hipStreamSynchronize(c->render);
         (void)hipStreamSynchronize(c->copy);
         (void)hipStreamSynchronize(c->copy2);
@@ -455,7 +427,6 @@ static size_t trim_idle(int device) {
             c->d_buf[i] = nullptr;
             c->d_cap[i] = 0;
         }
-        if (prev >= 0) (void)hipSetDevice(prev);
     }
     if (!idle.empty()) {
         {
@@ -486,7 +457,7 @@ int rt_reset_contexts(void) {
         for (const HostBlock &b : fr) (void)hipHostFree(b.p);
     }
     for (rt_ctx *c : dead) {
-        (void)hipSetDevice(c->device);
+        DevGuard g(c->device);
         (void)hipStreamSynchronize(c->render);
         (void)hipStreamSynchronize(c->copy);
         (void)hipStreamSynchronize(c->copy2);
@@ -503,19 +474,9 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, 
     if (width == 0 || height == 0) return RT_EBADARG;
     if (!out_rgb) return RT_EBADARG;
     rt_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.ndev = 1;
-    o.row_block = 16;
-    o.spp = 1;
-    if (opts && opts->struct_size) {
-        std::memcpy(&o, opts, opts->struct_size < sizeof(o) ? opts->struct_size : sizeof(o));
-        if (o.row_block == 0) o.row_block = 16;
-        if (o.ndev == 0) o.ndev = 1;
-        if (opts->struct_size < offsetof(rt_opts, spp) + sizeof(o.spp) || o.spp == 0) o.spp = 1; // ABI 1 callers
-    }
+    rt_opts_load(opts, &o);
     const bool integer = o.precision == RT_OUT_U8 || o.precision == RT_OUT_U16;
     if (o.precision != RT_OUT_F64 && o.precision != RT_OUT_F32 && !integer) return RT_EBADARG;
-    if (o.max_value == 0) o.max_value = 255; // also a struct_size that ends before the field
     if (integer && o.max_value > (o.precision == RT_OUT_U8 ? 255u : (uint32_t)RT_MAX_INT_VALUE)) return RT_ETOOBIG;
     if (o.order != RT_ORDER_EXACT && o.order != RT_ORDER_FAST) return RT_EBADARG;
     if (o.spp > RT_MAX_SPP) return RT_ETOOBIG;
@@ -561,20 +522,16 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, 
     if ((slab + band - 1) / band > max_nb) band = ((slab + max_nb - 1) / max_nb + gran - 1) / gran * gran;
     const uint32_t nb = (slab + band - 1) / band;
 
-    int prev = -1;
-    (void)hipGetDevice(&prev);
+    DevGuard restore; // (the loops below select each context's device themselves)
     std::vector<rt_ctx *> ctx(nd, nullptr);
     std::vector<char *> d_out(nd, nullptr), stage(nd, nullptr); // d_out: the slabs the copies read
     std::vector<char *> d_ren(nd, nullptr);                     // the slabs the kernels render into
     std::vector<uint8_t *> d_lv(nd, nullptr);
     std::vector<uint64_t *> d_cl(nd, nullptr);
-    // image rows of shard s = its slab rows [0, valid): the rest of the slab is never rendered
-    auto valid_rows = [&](uint32_t s) -> uint32_t {
-        const uint64_t start = (uint64_t)s * rb, period = (uint64_t)ns * rb;
-        if (height <= start) return 0;
-        const uint64_t full = (height - start) / period, rem = (height - start) % period;
-        return (uint32_t)(full * rb + std::min<uint64_t>(rem, rb));
-    };
+    // what every shard renders (its index filled in per shard): the window, in render_prec
+    rt_frame frame = rt_opts_frame(o, img_w, img_h, win, depth);
+    frame.nshards = ns;
+    frame.precision = render_prec;
     int err = RT_OK;
     auto shards_of = [&](uint32_t d) { return (ns - d + nd - 1) / nd; }; // shards d, d + nd, ...
     for (uint32_t d = 0; d < nd && err == RT_OK; ++d) {
@@ -586,40 +543,37 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, 
         const uint32_t k = shards_of(d);
         // an allocation that fails while other contexts of the device sit idle on their memory is
         // retried once after those are trimmed (trim_idle)
-        err = rt_ctx_device_buffer(c, 0, k * rslab_bytes, reinterpret_cast<void **>(&d_ren[d]));
-        if (err == RT_ENOMEM && trim_idle(dev) > 0)
-            err = rt_ctx_device_buffer(c, 0, k * rslab_bytes, reinterpret_cast<void **>(&d_ren[d]));
+        auto retry = [&](auto &&alloc) {
+            int e = alloc();
+            if (e == RT_ENOMEM && trim_idle(dev) > 0) e = alloc();
+            return e;
+        };
+        auto buffer = [&](int which, size_t bytes, void *out) {
+            return retry([&] { return rt_ctx_device_buffer(c, which, bytes, static_cast<void **>(out)); });
+        };
+        err = buffer(0, k * rslab_bytes, &d_ren[d]);
         d_out[d] = d_ren[d];
         if (err == RT_OK && integer) {
-            err = rt_ctx_device_buffer(c, 2, k * slab_bytes, reinterpret_cast<void **>(&d_out[d]));
-            if (err == RT_ENOMEM && trim_idle(dev) > 0)
-                err = rt_ctx_device_buffer(c, 2, k * slab_bytes, reinterpret_cast<void **>(&d_out[d]));
+            err = buffer(2, k * slab_bytes, &d_out[d]);
             if (err == RT_OK) err = rt_ctx_clamped(c, &d_cl[d]);
             if (err == RT_OK && hipMemsetAsync(d_cl[d], 0, sizeof(uint64_t), c->render) != hipSuccess) err = RT_EHIP;
         }
-        if (err == RT_OK && o.out_levels) {
-            err = rt_ctx_device_buffer(c, 1, (size_t)k * slab * width, reinterpret_cast<void **>(&d_lv[d]));
-            if (err == RT_ENOMEM && trim_idle(dev) > 0)
-                err = rt_ctx_device_buffer(c, 1, (size_t)k * slab * width, reinterpret_cast<void **>(&d_lv[d]));
-        }
+        if (err == RT_OK && o.out_levels) err = buffer(1, (size_t)k * slab * width, &d_lv[d]);
         if (err == RT_OK && !pinned) err = rt_ctx_host_buffer(c, 2 * (size_t)band * rowbytes, reinterpret_cast<void **>(&stage[d]));
         if (err != RT_OK) break;
         if (hipEventRecord(c->e0, c->render) != hipSuccess) err = RT_EHIP;
         // every band's render on the render stream, its copy on the copy stream behind it
         for (uint32_t i = 0; i < k && err == RT_OK; ++i) {
-            const uint32_t s = d + i * nd;
+            frame.shard = d + i * nd;
             char *slab_out = d_out[d] + i * slab_bytes, *slab_ren = d_ren[d] + i * rslab_bytes;
             uint8_t *slab_lv = o.out_levels ? d_lv[d] + (size_t)i * slab * width : nullptr;
-            const uint32_t valid = valid_rows(s);
+            // image rows of the shard = its slab rows [0, valid): the rest of the slab is never rendered
+            const uint32_t valid = frame.valid_rows();
             for (uint32_t b = 0; b < nb && err == RT_OK; ++b) {
                 const uint32_t b0 = b * band, b1 = std::min(slab, b0 + band);
-                auto launch = [&] {
-                    return rt_launch_rows(c->p, img_w, img_h, depth, win.x0, win.y0, width, height, rb, s, ns, render_prec,
-                                          o.order, o.spp, o.seed, b0, b1, slab_ren, slab_lv, c->render,
-                                          (o.flags & RT_LEVELS_HIT) ? 1 : 0);
-                };
-                err = launch();
-                if (err == RT_ENOMEM && trim_idle(dev) > 0) err = launch(); // (a failed grow launches nothing)
+                err = retry([&] { // (a failed grow launches nothing)
+                    return rt_launch_rows(c->p, frame, b0, b1, slab_ren, slab_lv, c->render, (o.flags & RT_LEVELS_HIT) ? 1 : 0);
+                });
                 // integer frame: the band's image rows quantised behind its render, before its event
                 if (err == RT_OK && integer && b0 < std::min(b1, valid))
                     err = rt_quantize(slab_ren + (size_t)b0 * rrow, RT_OUT_F64,
@@ -630,8 +584,8 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, 
                     hipStream_t cs = ((i * nb + b) % copy_streams()) ? c->copy2 : c->copy;
                     if (hipStreamWaitEvent(cs, c->band[i * nb + b], 0) != hipSuccess) err = RT_EHIP;
                     if (err == RT_OK)
-                        err = scatter_rows_async(slab_out, b0, b1, rowbytes, height, rb, s, ns,
-                                                 static_cast<char *>(out_rgb), cs);
+                        err = rt_scatter_rows_async(slab_out, b0, b1, rowbytes, rt_shard_map{height, rb, frame.shard, ns},
+                                                    static_cast<char *>(out_rgb), hipMemcpyDeviceToHost, cs);
                 }
             }
         }
@@ -666,8 +620,8 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, 
             }
             uint32_t b0, b1;
             rows_of(j, b0, b1);
-            host_scatter(stage[d] + (size_t)(j & 1) * band * rowbytes, b0, b1 - b0, rowbytes, height, rb,
-                         d + (j / nb) * nd, ns, static_cast<char *>(out_rgb));
+            host_scatter(stage[d] + (size_t)(j & 1) * band * rowbytes, b0, b1 - b0, rowbytes,
+                         rt_shard_map{height, rb, d + (j / nb) * nd, ns}, static_cast<char *>(out_rgb));
             if (j + 2 < total) err = enqueue(j + 2);
         }
     }
@@ -683,8 +637,8 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, 
             break;
         }
         for (uint32_t i = 0; i < k; ++i)
-            host_scatter(reinterpret_cast<const char *>(tmp.data()) + (size_t)i * slab * width, 0, slab, width, height,
-                         rb, d + i * nd, ns, reinterpret_cast<char *>(o.out_levels));
+            host_scatter(reinterpret_cast<const char *>(tmp.data()) + (size_t)i * slab * width, 0, slab, width,
+                         rt_shard_map{height, rb, d + i * nd, ns}, reinterpret_cast<char *>(o.out_levels));
     }
     double kms = 0;
     uint64_t clamped = 0;
@@ -704,7 +658,6 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, 
         }
         rt_ctx_release(c);
     }
-    if (prev >= 0) (void)hipSetDevice(prev);
     if (stats) {
         stats->kernel_ms = kms;
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();

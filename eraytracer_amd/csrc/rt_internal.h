@@ -5,18 +5,10 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/rt_mi355x.h"
-
-// rt_launch_window restricted to slab rows [row_begin, min(row_end, slab rows)) of the window
-// (rt_render.hip): (width, height) is the image, (x0, y0, win_w, win_h) the window, on which the
-// slab, its rows and the buffers are sized.  row_begin must be a multiple of 16 (the tile height);
-// d_out / d_levels point at slab row 0.
-// levels_hit: d_levels gets the primary-hit mask (1 / 0) instead of the level count (RT_LEVELS_HIT).
-int rt_launch_rows(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t x0, uint32_t y0,
-                   uint32_t win_w, uint32_t win_h, uint32_t row_block, uint32_t shard, uint32_t nshards, int precision,
-                   int order, uint32_t spp, uint64_t seed, uint32_t row_begin, uint32_t row_end, void *d_out,
-                   uint8_t *d_levels, void *stream, int levels_hit = 0);
+#include "rt_shard.h"
 
 // The window an options block selects in a width x height image (o: the boundary's own copy, zero
 // past the caller's struct_size): win_w = win_h = 0 is the whole frame.  RT_EBADARG for exactly one
@@ -35,6 +27,84 @@ inline int rt_opts_window(const rt_opts &o, uint32_t width, uint32_t height, rt_
     *win = rt_window{o.win_x0, o.win_y0, o.win_w, o.win_h};
     return RT_OK;
 }
+
+// The caller's options block with every default filled in: fields past the caller's struct_size
+// (or all of them, for a null pointer or struct_size 0) are zero, then row_block 0 -> 16,
+// ndev 0 -> 1, spp 0 or cut off by struct_size (ABI 1 callers) -> 1, max_value 0 -> 255.  out gets
+// the full struct_size, so it can be handed on as an options block of its own.
+inline void rt_opts_load(const rt_opts *in, rt_opts *out) {
+    memset(out, 0, sizeof *out);
+    const size_t n = in ? in->struct_size : 0;
+    if (n) memcpy(out, in, n < sizeof *out ? n : sizeof *out);
+    out->struct_size = sizeof *out;
+    if (out->row_block == 0) out->row_block = 16;
+    if (out->ndev == 0) out->ndev = 1;
+    if (n < offsetof(rt_opts, spp) + sizeof out->spp || out->spp == 0) out->spp = 1;
+    if (out->max_value == 0) out->max_value = 255;
+}
+
+// What one launch renders: the window `win` of an img_w x img_h image, as shard `shard` of
+// `nshards` interleaved in blocks of row_block rows.  The slab, its rows, the tiles and every
+// buffer are sized on the window; the image and the window's origin only place the rays.
+struct rt_frame {
+    uint32_t img_w, img_h;
+    rt_window win;
+    uint32_t depth, row_block, shard, nshards;
+    int precision, order;
+    uint32_t spp;
+    uint64_t seed;
+    uint32_t slab_rows() const { return rt_shard_slab_rows(win.h, row_block, nshards); }
+    // the slab rows inside the window, a prefix of the slab
+    uint32_t valid_rows() const { return rt_shard_valid_rows(win.h, row_block, shard, nshards); }
+};
+// The frame an options block asks for, as its single shard in binary64 (rt_render fills in its
+// own shards and precision).
+inline rt_frame rt_opts_frame(const rt_opts &o, uint32_t img_w, uint32_t img_h, const rt_window &win, uint32_t depth) {
+    rt_frame f = {};
+    f.img_w = img_w;
+    f.img_h = img_h;
+    f.win = win;
+    f.depth = depth;
+    f.row_block = o.row_block;
+    f.shard = 0;
+    f.nshards = 1;
+    f.precision = RT_OUT_F64;
+    f.order = o.order;
+    f.spp = o.spp;
+    f.seed = o.seed;
+    return f;
+}
+// The size, shard and window checks of every launch (rt_render.hip): RT_OK, RT_DONE (an image, a
+// window and an origin that are all zero) or an error; nothing is dereferenced, no HIP call is made.
+int rt_frame_check(const rt_frame &f);
+
+// Slab rows [row_begin, min(row_end, slab rows)) of frame f (rt_render.hip): the boundary renders a
+// frame in row bands.  row_begin must be a multiple of 16 (the tile height); d_out / d_levels point
+// at slab row 0.
+// levels_hit: d_levels gets the primary-hit mask (1 / 0) instead of the level count (RT_LEVELS_HIT).
+int rt_launch_rows(rt_prepared *p, const rt_frame &f, uint32_t row_begin, uint32_t row_end, void *d_out,
+                   uint8_t *d_levels, void *stream, int levels_hit);
+
+// Async copy of slab rows [b0, b1) of shard m (a slab of row pitch rowbytes) to their rows of a
+// row-major image, on `st` (rt_host.hip; rt_unshard's and rt_render's scatter).  With several
+// shards the whole row blocks go as one strided copy and the partial block at the bottom of the
+// image as a second one; one shard's rows are the image's, one contiguous copy.
+int rt_scatter_rows_async(const char *slab, uint32_t b0, uint32_t b1, uint32_t rowbytes, const rt_shard_map &m,
+                          char *image, hipMemcpyKind kind, hipStream_t st);
+
+struct DevGuard { // make `dev` the current device; restore the caller's on scope exit
+    int prev = -1;
+    bool ok = true; // dev could be selected
+    DevGuard() { // only save and restore: the scope selects devices itself
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    }
+    explicit DevGuard(int dev) : DevGuard() { ok = hipSetDevice(dev) == hipSuccess; }
+    DevGuard(const DevGuard &) = delete;
+    DevGuard &operator=(const DevGuard &) = delete;
+    ~DevGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
 
 // Replace the scene of a prepared context in place (its work space, streams and events are
 // kept; captured frame graphs are invalidated).  No launch of p may be in flight.

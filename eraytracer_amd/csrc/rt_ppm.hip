@@ -300,13 +300,7 @@ int rt_render_ppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_
     if (width == 0 && height == 0) return RT_DONE;
     if (width == 0 || height == 0) return RT_EBADARG;
     rt_opts o;
-    std::memset(&o, 0, sizeof o);
-    o.ndev = 1;
-    o.row_block = 16;
-    o.spp = 1;
-    if (opts && opts->struct_size) std::memcpy(&o, opts, opts->struct_size < sizeof o ? opts->struct_size : sizeof o);
-    if (o.spp == 0) o.spp = 1;
-    if (o.row_block == 0) o.row_block = 16;
+    rt_opts_load(opts, &o);
     o.precision = RT_OUT_F64; // the reference's values: the text is byte-exact
     o.out_levels = nullptr;
     FILE *f = nullptr;
@@ -325,8 +319,6 @@ int rt_render_ppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_
         std::fclose(f);
         return rc;
     }
-    int prev = -1;
-    (void)hipGetDevice(&prev);
     int nd = 0;
     if (hipGetDeviceCount(&nd) != hipSuccess || o.first_dev < 0 || o.first_dev >= nd) return RT_ENODEV;
     // the process's render context for this device (rt_host.hip): scene, streams, frame and text
@@ -334,7 +326,8 @@ int rt_render_ppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_
     rt_ctx *ctx = nullptr;
     rc = rt_ctx_acquire(o.first_dev, scene, n, &ctx);
     if (rc != RT_OK) return rc;
-    (void)hipSetDevice(o.first_dev);
+    DevGuard g(o.first_dev);
+    const rt_frame frame = rt_opts_frame(o, img_w, img_h, win, depth);
     const size_t frame_bytes = (size_t)width * height * 3 * sizeof(double);
     const size_t cap = rt_ppm_bound(width, height, max_value);
     void *d_rgb = nullptr, *d_text = nullptr, *h_text = nullptr;
@@ -343,8 +336,7 @@ int rt_render_ppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_
     do {
         if ((rc = rt_ctx_device_buffer(ctx, 0, frame_bytes, &d_rgb)) != RT_OK) break;
         if ((rc = rt_ctx_device_buffer(ctx, 2, cap, &d_text)) != RT_OK) break;
-        rc = rt_launch_window(rt_ctx_prepared(ctx), img_w, img_h, depth, win.x0, win.y0, width, height, o.row_block, 0, 1,
-                              RT_OUT_F64, o.order, o.spp, o.seed, d_rgb, nullptr, st);
+        rc = rt_launch_rows(rt_ctx_prepared(ctx), frame, 0, ~0u, d_rgb, nullptr, st, 0);
         if (rc != RT_OK) break;
         rc = rt_ppm_format(d_rgb, RT_OUT_F64, width, height, max_value, static_cast<char *>(d_text), cap, &len, st);
         if (rc == RT_ERANGE) { // a colour BEAM would print as a bignum: format on the host
@@ -367,7 +359,6 @@ int rt_render_ppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_
     if (f) std::fclose(f);
     (void)hipStreamSynchronize(st);
     rt_ctx_release(ctx);
-    if (prev >= 0) (void)hipSetDevice(prev);
     if (stats && rc == RT_OK) {
         stats->pixels = (uint64_t)width * height;
         stats->ndev = 1;

@@ -372,14 +372,7 @@ int rt_render_rawppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint
     if (max_value == 0) return RT_EBADARG;
     if (max_value > RT_MAX_INT_VALUE) return RT_ETOOBIG;
     rt_opts o;
-    std::memset(&o, 0, sizeof o);
-    o.ndev = 1;
-    o.row_block = 16;
-    o.spp = 1;
-    if (opts && opts->struct_size) std::memcpy(&o, opts, opts->struct_size < sizeof o ? opts->struct_size : sizeof o);
-    if (o.spp == 0) o.spp = 1;
-    if (o.row_block == 0) o.row_block = 16;
-    if (o.ndev == 0) o.ndev = 1;
+    rt_opts_load(opts, &o);
     rt_window win;
     int rc = rt_opts_window(o, img_w, img_h, &win);
     if (rc != RT_OK) return rc;
@@ -388,7 +381,6 @@ int rt_render_rawppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint
     const int fmt = max_value > 255 ? RT_OUT_U16 : RT_OUT_U8;
     const size_t osz = fmt == RT_OUT_U16 ? 2 : 1;
     const size_t nval = (size_t)width * height * 3;
-    o.struct_size = sizeof o;
     o.precision = fmt;
     o.max_value = max_value;
     o.out_levels = nullptr;
@@ -402,14 +394,13 @@ int rt_render_rawppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint
         if (st.flags & RT_STATS_CLAMPED) return RT_ERANGE; // P3 would print a negative number
         return write_p6(path, width, height, max_value, img.data());
     }
-    int prev = -1;
-    (void)hipGetDevice(&prev);
     int nd = 0;
     if (hipGetDeviceCount(&nd) != hipSuccess || o.first_dev < 0 || o.first_dev >= nd) return RT_ENODEV;
     rt_ctx *ctx = nullptr;
     rc = rt_ctx_acquire(o.first_dev, scene, n, &ctx);
     if (rc != RT_OK) return rc;
-    (void)hipSetDevice(o.first_dev);
+    DevGuard g(o.first_dev);
+    const rt_frame frame = rt_opts_frame(o, img_w, img_h, win, depth);
     void *d_rgb = nullptr, *d_int = nullptr, *h_int = nullptr;
     uint64_t *d_clamped = nullptr;
     uint64_t clamped = 0;
@@ -420,8 +411,7 @@ int rt_render_rawppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint
         if ((rc = rt_ctx_clamped(ctx, &d_clamped)) != RT_OK) break;
         if ((rc = rt_ctx_host_buffer(ctx, nval * osz, &h_int)) != RT_OK) break;
         if (hipMemsetAsync(d_clamped, 0, sizeof clamped, st) != hipSuccess) { rc = RT_EHIP; break; }
-        rc = rt_launch_window(rt_ctx_prepared(ctx), img_w, img_h, depth, win.x0, win.y0, width, height, o.row_block, 0, 1,
-                              RT_OUT_F64, o.order, o.spp, o.seed, d_rgb, nullptr, st);
+        rc = rt_launch_rows(rt_ctx_prepared(ctx), frame, 0, ~0u, d_rgb, nullptr, st, 0);
         if (rc != RT_OK) break;
         if ((rc = rt_quantize(d_rgb, RT_OUT_F64, nval, max_value, fmt, d_int, d_clamped, st)) != RT_OK) break;
         // the samples and the counter to pinned memory by DMA; the file is written from there
@@ -433,7 +423,6 @@ int rt_render_rawppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint
     } while (0);
     (void)hipStreamSynchronize(st);
     rt_ctx_release(ctx);
-    if (prev >= 0) (void)hipSetDevice(prev);
     if (stats && (rc == RT_OK || rc == RT_ERANGE)) {
         stats->pixels = (uint64_t)width * height;
         stats->ndev = 1;

@@ -4,6 +4,11 @@
 // arguments): the device code lives in the rt_*.inc fragments included below, inside the anonymous
 // namespace and in order of dependence; this file is the host side — rt_prepared and its work
 // space, the choice of engine and kernel template, frame graphs and the C-ABI entry points.
+// Every launch is described by one rt_frame (rt_internal.h) from the entry point down to the
+// kernels' arguments.  The wavefront engine's host side is a plan and four stages: wave_plan (the
+// mode, the sizes, the LDS layout: no HIP call), wave_grow, wave_pmask and wave_pass, the last
+// built of wave_level_lists, wave_reflect and wave_walks; launch_sample_passes is the one loop
+// over the samples of a supersampled band.
 //
 // One work-item per pixel; a wave covers an 8x8 pixel tile (coherent rays), a 256-thread
 // workgroup a 16x16 tile.  Per pixel the kernel runs trace_ray_through_pixel/3
@@ -149,17 +154,6 @@ struct rt_prepared {
 
 namespace {
 
-struct DevGuard { // restore the caller's current device on scope exit
-    int prev = -1;
-    explicit DevGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        (void)hipSetDevice(dev);
-    }
-    ~DevGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 // RT_CFG_CULL = 0: every scan tests every object (no wave beams or cones, no occluder masks, no
 // BVH, no LDS-staged tables, no host-proven skips of range checks) — the reference's brute-force
 // scans, against which the filters' frames are checked bit for bit (tests/test_gpu_frames.py).
@@ -298,9 +292,16 @@ auto with_sph(bool staged, bool sph_only, F &&f) {
     return with_int<0, 2>(staged ? 2 : sph_only ? 1 : 0, f);
 }
 
+// The image a frame's window lies in, as the kernels take it.
+ImageGeom image_geom(const rt_frame &f) { return ImageGeom{(int)f.img_w, (int)f.img_h, (int)f.win.x0, (int)f.win.y0}; }
+
+// The fused engine: slab rows [row0, row_end) of f in one k_render launch.
 template <int ORDER, int PREC, bool GENPOW>
-int launch_t(rt_prepared *p, int W, int H, const ImageGeom &im, int depth, int rb, int shard, int nshards, int row0,
-             int row_end, void *out, uint8_t *levels, hipStream_t st, int levels_hit) {
+int launch_t(rt_prepared *p, const rt_frame &f, int row0, int row_end, void *out, uint8_t *levels, hipStream_t st,
+             int levels_hit) {
+    const int W = (int)f.win.w, H = (int)f.win.h, depth = (int)f.depth;
+    const int rb = (int)f.row_block, shard = (int)f.shard, nshards = (int)f.nshards;
+    const ImageGeom im = image_geom(f);
     dim3 grid((W + TILE - 1) / TILE, (row_end - row0 + TILE - 1) / TILE);
     size_t lds = ORDER == RT_ORDER_EXACT ? (size_t)depth * BLOCK * 12 + (size_t)BLOCK * 24 : 0;
     KtScope kt(p, RT_KT_RENDER, st);
@@ -423,9 +424,7 @@ int rt_scene_canon(rt_elem *scene, uint32_t n) { return fill_canon(scene, n); }
 
 uint32_t rt_shard_rows(uint32_t height, uint32_t row_block, uint32_t nshards) {
     if (row_block == 0 || nshards == 0) return 0;
-    uint64_t span = (uint64_t)row_block * nshards;
-    uint64_t blocks = (height + span - 1) / span;
-    return (uint32_t)(blocks * row_block);
+    return rt_shard_slab_rows(height, row_block, nshards);
 }
 
 int rt_prepare(const rt_elem *scene, uint32_t n, int device, rt_prepared **out) {
@@ -584,59 +583,34 @@ int side_stream(rt_prepared *p, int depth) {
     return RT_OK;
 }
 
-// The slab rows of shard sh that lie inside the image (a prefix of the slab).
-size_t valid_slab_rows(int H, int rb, int sh, int ns) {
-    const size_t slab = rt_shard_rows((uint32_t)H, (uint32_t)rb, (uint32_t)ns);
-    size_t v = 0;
-    for (size_t blk = 0; blk * rb < slab; ++blk) {
-        const long long base = ((long long)blk * ns + sh) * rb;
-        v += (size_t)std::max(0LL, std::min((long long)rb, (long long)H - base));
-    }
-    return v;
-}
+// ---- the wavefront engine's host side: a plan (pure arithmetic), the work space grown from it,
+// the primary-mask cache, and one function per stage of a row pass.
 
-// Does a wavefront pass write every pixel exactly once?  Yes with k_reflect_shade (the colours of
-// records with a reflection hit are left to k_walk) and without reflections; no when k_light
-// shades level 0 provisionally beside the chain (side streams, or levels requested).
-bool wave_single_write(const rt_prepared *p, int D, bool levels) {
-    const int nrefl = (p->hdr.n_light > 0 && D > 1) ? D - 1 : 0;
-    const bool overlap = lit_overlap(p) && D > 1 && p->hdr.n_light > 0;
-    return nrefl == 0 || (!overlap && !levels);
-}
-
-// acc (slab row 0, binary64, or null): supersampled passes fold their sample into it where each
-// pixel is written (put_pixel) — only valid when wave_single_write holds.  keep (RT_PROGRESSIVE):
-// such a pass only accumulates, whatever its sample — `out` is then never written.
-// W x H is the raster the call renders (slabs, tiles, queues and stores are sized on it): a window
-// of the image `im`, the whole frame being {W, H, 0, 0}.
-template <int PREC, bool GENPOW>
-int launch_wavefront(rt_prepared *p, int W, int H, const ImageGeom &im, int D, int rb, int sh, int ns, int row_begin,
-                     int row_end, void *out, uint8_t *levels, hipStream_t st, int spp = 1, int sample = 0,
-                     unsigned long long seed = 0, double *acc = nullptr, int levels_hit = 0, bool keep = false) {
-    // renders slab rows [row_begin, row_end) (row_begin a multiple of TILE); out / levels point at slab row 0.
+// What tells one pass over a band from another when a pixel is sampled more than once.
+struct WaveSample {
+    int sample = 0, spp = 1;
+    unsigned long long seed = 0;
+    // acc (slab row 0, binary64, or null): the pass folds its sample into it where each pixel is
+    // written (put_pixel) — only valid when WavePlan::single_write holds
+    double *acc = nullptr;
+    // keep (RT_PROGRESSIVE): the pass only accumulates, whatever its sample — `out` is never written
+    bool keep = false;
     // levels_hit: k_primary writes the primary-hit mask (what it always writes: 1 on a hit, 0 on a
     // miss) and the later kernels do not count levels, so the fused path stays on
-    uint8_t *const levels_primary = levels;
-    const SceneHdr &hdr = p->hdr;
-    if (levels_hit) levels = nullptr;
-    const int slab_rows = row_end - row_begin;
-    const int nlev = D > 0 ? D : 1;
-    const size_t per_row = (size_t)W * nlev * sizeof(HitRec);
-    int pass_rows = (int)std::min<size_t>((size_t)slab_rows, std::max<size_t>(TILE, queue_budget() / per_row));
-    pass_rows = std::max(TILE, pass_rows / TILE * TILE);
-    if (pass_rows > slab_rows) pass_rows = slab_rows;
-    const int tiles_x = (W + TILE - 1) / TILE;
-    const size_t max_tiles = (size_t)tiles_x * ((pass_rows + TILE - 1) / TILE);
-    const size_t slots = max_tiles * TILE_SLOTS; // per level
-    int rc = grow(p, rt_prepared::W_QUEUE, slots * nlev * sizeof(HitRec));
-    // colours of levels 1 .. depth-1, COL_W doubles per slot (level 0 goes straight to the
-    // frame), and per level the has-a-child flags
-    const size_t col_doubles = slots * COL_W * (size_t)std::max(1, nlev - 1);
-    const bool overlap = lit_overlap(p) && D > 1 && p->hdr.n_light > 0;
-    const int nrefl = (p->hdr.n_light > 0 && D > 1) ? D - 1 : 0;
+    int levels_hit = 0;
+};
+
+// Everything a launch of slab rows [row_begin, row_end) decides before it touches the device.
+struct WavePlan {
+    int row_begin, row_end;
+    int nlev;          // queued levels: the depth, at least 1
+    bool count_levels; // the kernels after k_primary count levels (levels wanted, and not just the hit mask)
+    // shading beside the reflection chain on the side streams (level 0 provisionally, by k_light)
+    bool overlap;
+    int nrefl, nshade; // reflection levels; shaded levels
     // no side streams (frames in flight): each level's shading fused into the next reflection
     // pass (k_reflect_shade)
-    const bool fuse = !overlap && !levels && nrefl > 0;
+    bool fuse;
     // Inline walks (k_reflect_shade's iw, levels >= 1): every level is shaded by the launch that
     // reflects it; the chain of a shaded record without a child is walked by that launch, and the
     // deepest level's hits are shaded and walked by the launch that finds them (not queued) — what
@@ -644,11 +618,10 @@ int launch_wavefront(rt_prepared *p, int W, int H, const ImageGeom &im, int D, i
     // and their re-reads.  Needs the shadow answers in the records (<= 32 lights) and two reflection
     // levels or more (level 1's kernel, the dominant one, is left as is).  For S64 the dense
     // arrangement this implies measured the same as the sparse one (profiles/r05aa_ab_memset_dense.txt).
-    const bool iw = fuse && p->hdr.n_light <= 32 && nrefl >= 2;
+    bool iw;
     // spheres only, culling on: every shadow target has occluder masks (lit_by<1>); their
     // per-lane-gathered tables staged in each workgroup's LDS when they fit (SPH = 2)
-    const bool sph_only = p->hdr.n_tri == 0 && p->hdr.n_pl == 0 && p->hdr.cull_ok && p->hdr.occ_ok;
-    const bool staged = sph_only && p->hdr.l_bytes > 0;
+    bool sph_only, staged;
     // ... and for LDS-staged scenes of up to TERM_MAX_LIGHTS lights those walks fold the child's
     // colour into per-light terms stored at the first shading instead of shading again (walk_fold):
     // one entry per slot of the queued levels 1 .. nrefl-1.  An inline-walk launch writes no colour
@@ -656,234 +629,359 @@ int launch_wavefront(rt_prepared *p, int W, int H, const ImageGeom &im, int D, i
     // scenes only: S256 depth 8 with its tables in L2 and dense deep levels measured 2.7 % slower per
     // frame with the entries than reshading, profiles/terms_ab_c3.txt; only the SPH = 2 kernels
     // compile the entries in.)
-    const bool fold = iw && staged && p->hdr.n_light <= TERM_MAX_LIGHTS;
-    const size_t term_bytes =
-        fold ? slots * (size_t)(nrefl - 1) * term_stride(p->hdr.n_light) * sizeof(double2) : 0;
-    if (rc == RT_OK) rc = grow(p, rt_prepared::W_COLBUF, std::max(col_doubles * sizeof(double), term_bytes));
-    if (rc == RT_OK) rc = grow(p, rt_prepared::W_CHILD, slots * nlev);
-    if (rc == RT_OK) rc = grow(p, rt_prepared::W_LIT, slots * nlev * sizeof(unsigned));
-    if (rc == RT_OK) rc = grow(p, rt_prepared::W_COUNTS, max_tiles * nlev * sizeof(int));
-    // dense work lists: 64 per-level record counts, then per level the slots of its records in tile order
-    const size_t list0 = level_counts(nlev);
-    const size_t items_ints = list0 + slots * nlev;
-    if (rc == RT_OK) rc = grow(p, rt_prepared::W_ITEMS, items_ints * sizeof(int));
-    if (rc == RT_OK && overlap) rc = side_stream(p, D);
-    if (rc != RT_OK) return rc;
-    // the primary rays' candidate masks of the whole slab (k_pmask), recomputed only when the
-    // frame geometry — the raster's and the image's: two windows of one size at different origins
-    // see different rays — or the scene changed (or after rt_trim)
-    const unsigned long long *pmask = nullptr;
-    const unsigned short *pempty = nullptr; // after the masks: one byte per half-tile, 1 = every mask zero
-    if (p->hdr.beam_ok && D > 0) {
-        const int slab_all = (int)rt_shard_rows(H, rb, ns);
-        const size_t nhalf = (size_t)tiles_x * ((slab_all + TILE - 1) / TILE) * 2;
-        const long long key[12] = {W, H, rb, sh, ns, spp > 1, (long long)p->scene_gen, slab_all, im.IW, im.IH, im.x0, im.y0};
-        if (!(p->pmask_valid && std::memcmp(key, p->pmask_key, sizeof(key)) == 0)) {
-            p->pmask_valid = false;
-            // New masks (and perhaps a new buffer): a frame graph captured with the old ones holds
-            // no k_pmask launch and would read these, so it is invalidated (gen).
-            ++p->gen;
-            if ((rc = grow(p, rt_prepared::W_PMASK, nhalf * p->hdr.n_chunk * 8 + nhalf)) != RT_OK) return rc;
-            const dim3 pg((unsigned)std::min<size_t>(4096, (nhalf + 3) / 4));
-            KtScope kt(p, RT_KT_PMASK, st);
-            with_bool(spp > 1, [&](auto ss) {
-                hipLaunchKernelGGL(k_pmask<decltype(ss)::value>, pg, dim3(256), 0, st, hdr, p->d_tab, p->d_itab, W, H,
-                                   rb, sh, ns, slab_all, (int)nhalf, p->buf<unsigned long long>(rt_prepared::W_PMASK),
-                                   reinterpret_cast<unsigned char *>(p->buf<unsigned long long>(rt_prepared::W_PMASK) +
-                                                           nhalf * p->hdr.n_chunk),
-                                   im);
-            });
-            HIPCHK(hipGetLastError());
-            std::memcpy(p->pmask_key, key, sizeof(key));
-            p->pmask_valid = true;
-        }
-        pmask = p->buf<unsigned long long>(rt_prepared::W_PMASK);
-        pempty = reinterpret_cast<const unsigned short *>(pmask + nhalf * p->hdr.n_chunk);
-    }
-    // streams of the shading pass: level 0 (the bulk) beside the whole reflection chain, the
-    // next levels each on their own, so no level waits for another's shading
-    auto ls = [&](int k) { return overlap ? p->side[std::min(k, 1)] : st; };
-    HitRec *const q = p->buf<HitRec>(rt_prepared::W_QUEUE);
-    double *const d_colbuf = p->buf<double>(rt_prepared::W_COLBUF);
-    uint8_t *const d_child = p->buf<uint8_t>(rt_prepared::W_CHILD);
-    unsigned *const d_lit = p->buf<unsigned>(rt_prepared::W_LIT);
-    int *const d_counts = p->buf<int>(rt_prepared::W_COUNTS);
-    int *const d_items = p->buf<int>(rt_prepared::W_ITEMS);
-    const int nshade = D > 0 ? 1 + nrefl : 0;
-    const size_t lds = staged ? (size_t)p->hdr.l_bytes : 0; // the SPH = 2 kernels' dynamic LDS; 0 for SPH < 2
-    // Reflection kernels of levels that traverse the sphere BVH: after the staged tables in LDS,
-    // the BVH nodes and sphere rows (when they fit BVH_LDS_MAX) and every lane's stack.
-    SceneHdr rhdr = hdr;
-    size_t lds_bvh = lds;
-    if (rhdr.bvh_ok) {
-        const size_t nb = (size_t)rhdr.n_bvh * BVH_NODE_DOUBLES * 8, sb = (size_t)rhdr.n_sph * SPH_W * 8;
-        if (nb + sb <= (size_t)BVH_LDS_MAX) {
-            rhdr.l_bvh = (int)lds_bvh;
-            rhdr.l_bsph = (int)(lds_bvh + nb);
-            lds_bvh += nb + sb;
-        }
-        rhdr.l_stack = (int)lds_bvh;
-        lds_bvh += (size_t)BLOCK * rhdr.bvh_depth * sizeof(unsigned);
-    }
+    bool fold;
+    int pass_rows, tiles_x; // rows per pass (queue memory is bounded, queue_budget), tiles per tile row
+    size_t slots, list0;    // record slots per level of a pass; ints before the dense lists in W_ITEMS
+    size_t bytes[rt_prepared::W_COUNT]; // the work space a pass needs (0: not this plan's to grow)
+    // the primary rays' candidate masks (k_pmask), of the whole slab: half-tiles, bytes (0: no masks)
+    int slab_all;
+    size_t nhalf, pmask_bytes;
+    // dynamic LDS: the SPH = 2 kernels' staged tables (0 for SPH < 2); for the reflection kernels of
+    // levels that traverse the sphere BVH, after them the BVH nodes and sphere rows (when they fit
+    // BVH_LDS_MAX) and every lane's stack, at the offsets rhdr carries
+    size_t lds, lds_bvh;
+    SceneHdr rhdr;
     // (LDS-staged scenes keep the candidate walks: their tables and the BVH would not fit together)
-    auto bvh_at = [&](int k) { return !staged && rhdr.bvh_ok && k >= rhdr.bvh_level; };
-    auto lds_r = [&](int k) { return bvh_at(k) ? lds_bvh : lds; };
-    double2 *const d_terms = fold ? reinterpret_cast<double2 *>(d_colbuf) : nullptr;
-    for (int row0 = row_begin; row0 < row_end; row0 += pass_rows) {
-        const int rows = std::min(pass_rows, row_end - row0);
-        const int ntiles = tiles_x * ((rows + TILE - 1) / TILE);
-        // the pass covers slab rows [row0, row0 + rows): out/levels offset to row0; the
-        // kernels map slab rows to image rows through the shard interleave themselves
-        const size_t off = (size_t)row0 * W;
-        void *o = static_cast<char *>(out) + off * 3 * (PREC == RT_OUT_F64 ? 8 : 4);
-        uint8_t *lv = levels ? levels + off : nullptr;
-        uint8_t *lv0 = levels_primary ? levels_primary + off : nullptr; // k_primary's
-        double *acc_p = acc ? acc + off * 3 : nullptr;
-        auto qk = [&](int k) { return q + (size_t)k * ntiles * TILE_SLOTS; };
-        auto ck = [&](int k) { return d_counts + (size_t)k * ntiles; };
-        int *nitems = d_items; // [0, 64): per-level record counts
-        int *lists = d_items + list0;
-        auto ik = [&](int k) { return lists + (size_t)k * ntiles * TILE_SLOTS; };
-        auto colk = [&](int k) { return k > 0 ? d_colbuf + (size_t)(k - 1) * ntiles * TILE_SLOTS * COL_W : nullptr; };
-        auto chk = [&](int k) { return d_child + (size_t)k * ntiles * TILE_SLOTS; };
-        auto litk = [&](int k) { return d_lit + (size_t)k * ntiles * TILE_SLOTS; };
-        const dim3 iblocks((ntiles + ITEMS_BLOCK - 1) / ITEMS_BLOCK);
-        const int smp = sample_arg(sample, keep);
-        const PassGeom g = make_pass_geom(W, im, rb, sh, ns, row0, spp, smp, seed, acc_p); // level-0 records are rebuilt from it
-        const dim3 grid(std::min(ntiles, PRIMARY_GRID)); // k_primary: grid-stride loop over the tiles
-        {
-            KtScope kt(p, RT_KT_PRIMARY, st);
-            with_bool(lv0 != nullptr, [&](auto has_lv) { // (without lv0 there is no lv either)
-                hipLaunchKernelGGL((k_primary<PREC, decltype(has_lv)::value>), grid, dim3(PRIMARY_BLOCK), 0, st, hdr,
-                                   p->d_tab, p->d_itab, W, im.y0 + H, D, rb, g.yoff, ns, rows, row0, o, lv0, q, d_counts, ntiles,
-                                   spp, smp, seed, acc_p, pmask, pempty, nitems, g.img);
-            });
-        }
-        HIPCHK(hipGetLastError());
-        const int sblocks = std::min<int>(STRIDE_BLOCKS, (ntiles * (TILE_SLOTS / 64) + BLOCK / 64 - 1) / (BLOCK / 64));
-        const int sblocks1 = std::min<int>(STRIDE_BLOCKS_L1, (ntiles * (TILE_SLOTS / 64) + BLOCK / 64 - 1) / (BLOCK / 64));
-        const int sblocksw = std::min<int>(STRIDE_BLOCKS_WALK, (ntiles * (TILE_SLOTS / 64) + BLOCK / 64 - 1) / (BLOCK / 64));
-        const int sblocksb = std::min<int>(STRIDE_BLOCKS_BVH, (ntiles * (TILE_SLOTS / 64) + BLOCK / 64 - 1) / (BLOCK / 64));
-        // level k's dense list, then its shading (k_light reads only level k: on a side stream
-        // it starts as soon as the list exists and runs beside the next reflections)
-        auto level_lists = [&](int k) -> int {
-            // (inline walks: the deepest level is shaded by the launch that finds its hits, never queued)
-            if (iw && k == nrefl) return RT_OK;
-            hipLaunchKernelGGL(k_items, iblocks, dim3(ITEMS_BLOCK), 0, st, ck(k), ntiles, ik(k), nitems + k);
-            HIPCHK(hipGetLastError());
-            if (overlap) {
-                HIPCHK(hipEventRecord(p->ev_level[k], st));
-                HIPCHK(hipStreamWaitEvent(ls(k), p->ev_level[k], 0));
-            }
-            if (fuse && k < nrefl) return RT_OK; // shaded by k_reflect_shade(k + 1)
-            if (k == nrefl && k >= 2) { // the deepest level >= 2: shaded by k_walk_deep / k_walk
-                if (overlap) HIPCHK(hipEventRecord(p->ev_lit[k], ls(k)));
-                return RT_OK;
-            }
-            // levels >= 2 are shaded here only when dense (decided on the device; otherwise the
-            // launch exits at once): a smaller persistent grid keeps the empty launch cheap
-            const int lblocks = k >= 2 ? std::min(sblocks, DEEP_LIGHT_BLOCKS) : sblocks;
-            with_sph(staged, sph_only, [&](auto sph) {
-                hipLaunchKernelGGL((k_light<PREC, GENPOW, decltype(sph)::value>), dim3(lblocks), dim3(BLOCK), lds, ls(k),
-                                   hdr, p->d_tab, p->d_itab, k, o, qk(k), ik(k), nitems + k, colk(k), litk(k), g);
-            });
-            HIPCHK(hipGetLastError());
-            if (overlap) HIPCHK(hipEventRecord(p->ev_lit[k], ls(k)));
-            return RT_OK;
-        };
-        if (nshade > 0 && (rc = level_lists(0)) != RT_OK) return rc;
-        for (int k = 1; k <= nrefl; ++k) {
-            // level 1 (from the primary hits) is dense and throughput-bound; deeper levels are a few
-            // waves each, bound by one wave's dependent chain: they walk two candidates per step
-            KtScope kt(p, k == 1 ? RT_KT_LEVEL1 : 0, st);
-            if (fuse) {
-                // levels traversing the sphere BVH (unstaged scenes only) take the BVH instantiations,
-                // the deepest level with inline walks the LAST ones; both only come with ILP
-                const bool bvh_k = bvh_at(k), ilp = bvh_k || k != 1, last = ilp && iw && k == nrefl;
-                with_sph(staged, sph_only, [&](auto sph) {
-                    constexpr int SPH = decltype(sph)::value;
-                    auto rs = [&](auto ilp_c, auto bvh_c, auto last_c) {
-                        constexpr bool BVH = decltype(bvh_c)::value;
-                        hipLaunchKernelGGL(
-                            (k_reflect_shade<PREC, GENPOW, SPH, decltype(ilp_c)::value, BVH, decltype(last_c)::value>),
-                            dim3(k == 1 ? sblocks1 : BVH ? sblocksb : sblocks), dim3(BLOCK), lds_r(k), st, rhdr, p->d_tab,
-                            p->d_itab, k, o, qk(k - 1), ik(k - 1), nitems + (k - 1), qk(k), ck(k), iw ? nullptr : chk(k - 1),
-                            colk(k - 1), g, iw && k >= 2 ? (k == nrefl ? 2 : 1) : 0, d_terms);
-                    };
-                    auto rs_ilp = [&](auto bvh_c) {
-                        with_bool(last, [&](auto last_c) { rs(std::true_type{}, bvh_c, last_c); });
-                    };
-                    if (!ilp) rs(std::false_type{}, std::false_type{}, std::false_type{});
-                    else if constexpr (SPH == 2) rs_ilp(std::false_type{}); // (staged: never the BVH, bvh_at)
-                    else with_bool(bvh_k, rs_ilp);
-                });
-            } else {
-                with_bool(lv != nullptr, [&](auto has_lv) {
-                    with_bool(k != 1, [&](auto ilp_c) {
-                        hipLaunchKernelGGL((k_reflect<decltype(has_lv)::value, decltype(ilp_c)::value>), dim3(sblocks),
-                                           dim3(BLOCK), lds, st, rhdr, p->d_tab, p->d_itab, k, qk(k - 1), ik(k - 1),
-                                           nitems + (k - 1), qk(k), ck(k), lv, chk(k - 1), g);
-                    });
-                });
-            }
-            HIPCHK(hipGetLastError());
-            if ((rc = level_lists(k)) != RT_OK) return rc;
-        }
-        // Without side streams one k_walk finishes every chain (sparse deep levels shaded on the
-        // way).  With side streams (see deep_dense): k_walk_deep right after the chain; the chains
-        // ending at level 1 (the bulk) are finished on side stream 0 as soon as levels 0 and 1 are
-        // shaded, beside it; then the rest, once every level's shading is in (side stream 1
-        // shades levels 1.. in order: its last level's event covers them all)
-        if (nrefl > 0) {
-            const size_t ls_ = (size_t)ntiles * TILE_SLOTS;
-            const bool bits = p->hdr.n_light <= 32; // the shadow answers fit the record
-            // deep: the merged walk (no k_walk_deep; without side streams); after k_reflect_shade
-            // (fuse) the shadow answers are in the children's records (PAD)
-            auto walk = [&](hipStream_t s_, int lo, int hi, bool deep) {
-                with_sph(staged, sph_only, [&](auto sph) {
-                    with_bool(bits, [&](auto bits_c) {
-                        auto launch = [&](auto deep_c, auto pad_c) {
-                            hipLaunchKernelGGL((k_walk<PREC, GENPOW, decltype(sph)::value, decltype(bits_c)::value,
-                                                       decltype(deep_c)::value, decltype(pad_c)::value>),
-                                               dim3(sblocksw), dim3(BLOCK), lds, s_, hdr, p->d_tab, p->d_itab, D, o, q,
-                                               ls_, lists, nitems, d_colbuf, d_child, d_lit, lo, hi, g);
-                        };
-                        // (PAD is launched with DEEP and BITS only; its instantiations without BITS
-                        // exist, as they always have, and are never run)
-                        if (deep && fuse && bits) launch(std::true_type{}, std::true_type{});
-                        else if (deep) launch(std::true_type{}, std::false_type{});
-                        else launch(std::false_type{}, std::false_type{});
-                    });
-                });
-            };
-            if (overlap) { // side stream 0 (after level 0's shading) waits for level 1's, and for
-                           // k_reflect(2), which marks the level-1 records that have a child
-                HIPCHK(hipStreamWaitEvent(p->side[0], p->ev_lit[1], 0));
-                if (D > 2) HIPCHK(hipStreamWaitEvent(p->side[0], p->ev_level[2], 0));
-                walk(p->side[0], 1, 2, false);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipEventRecord(p->ev_lit[0], p->side[0]));
-            }
-            if (D > 2 && overlap) {
-                with_sph(staged, sph_only, [&](auto sph) {
-                    hipLaunchKernelGGL((k_walk_deep<GENPOW, decltype(sph)::value>), dim3(sblocks), dim3(BLOCK), lds, st,
-                                       hdr, p->d_tab, p->d_itab, D, q, ls_, lists, nitems, d_child, colk(2));
-                });
-                HIPCHK(hipGetLastError());
-            }
-            if (overlap) {
-                HIPCHK(hipStreamWaitEvent(st, p->ev_lit[nrefl], 0));
-                HIPCHK(hipStreamWaitEvent(st, p->ev_lit[0], 0));
-                if (D > 2) walk(st, 2, D, false);
-            } else if (!iw) {
-                walk(st, 1, D, true); // every chain in one launch, sparse deep levels shaded there too
-            }
-            HIPCHK(hipGetLastError());
-        } else if (overlap && nshade > 0) {
-            HIPCHK(hipStreamWaitEvent(st, p->ev_lit[0], 0));
-        }
+    bool bvh_at(int k) const { return !staged && rhdr.bvh_ok && k >= rhdr.bvh_level; }
+    size_t lds_r(int k) const { return bvh_at(k) ? lds_bvh : lds; }
+    // Does a pass write every pixel exactly once?  Yes with k_reflect_shade (the colours of records
+    // with a reflection hit are left to k_walk) and without reflections; no when k_light shades
+    // level 0 provisionally beside the chain (side streams, or levels requested).
+    bool single_write() const { return nrefl == 0 || (!overlap && !count_levels); }
+};
+
+WavePlan wave_plan(const rt_prepared *p, const rt_frame &f, int row_begin, int row_end, bool levels, int levels_hit) {
+    const SceneHdr &hdr = p->hdr;
+    const int W = (int)f.win.w, D = (int)f.depth;
+    WavePlan pl = {};
+    pl.row_begin = row_begin;
+    pl.row_end = row_end;
+    pl.nlev = D > 0 ? D : 1;
+    pl.count_levels = levels && !levels_hit;
+    const int slab_rows = row_end - row_begin;
+    const size_t per_row = (size_t)W * pl.nlev * sizeof(HitRec);
+    pl.pass_rows = (int)std::min<size_t>((size_t)slab_rows, std::max<size_t>(TILE, queue_budget() / per_row));
+    pl.pass_rows = std::max(TILE, pl.pass_rows / TILE * TILE);
+    if (pl.pass_rows > slab_rows) pl.pass_rows = slab_rows;
+    pl.tiles_x = (W + TILE - 1) / TILE;
+    const size_t max_tiles = (size_t)pl.tiles_x * ((pl.pass_rows + TILE - 1) / TILE);
+    const size_t slots = pl.slots = max_tiles * TILE_SLOTS;
+    pl.overlap = lit_overlap(p) && D > 1 && hdr.n_light > 0;
+    pl.nrefl = (hdr.n_light > 0 && D > 1) ? D - 1 : 0;
+    pl.nshade = D > 0 ? 1 + pl.nrefl : 0;
+    pl.fuse = !pl.overlap && !pl.count_levels && pl.nrefl > 0;
+    pl.iw = pl.fuse && hdr.n_light <= 32 && pl.nrefl >= 2;
+    pl.sph_only = hdr.n_tri == 0 && hdr.n_pl == 0 && hdr.cull_ok && hdr.occ_ok;
+    pl.staged = pl.sph_only && hdr.l_bytes > 0;
+    pl.fold = pl.iw && pl.staged && hdr.n_light <= TERM_MAX_LIGHTS;
+    // colours of levels 1 .. depth-1, COL_W doubles per slot (level 0 goes straight to the frame) —
+    // or the per-light terms — and per level the has-a-child flags
+    const size_t col_doubles = slots * COL_W * (size_t)std::max(1, pl.nlev - 1);
+    const size_t term_bytes =
+        pl.fold ? slots * (size_t)(pl.nrefl - 1) * term_stride(hdr.n_light) * sizeof(double2) : 0;
+    pl.bytes[rt_prepared::W_QUEUE] = slots * pl.nlev * sizeof(HitRec);
+    pl.bytes[rt_prepared::W_COLBUF] = std::max(col_doubles * sizeof(double), term_bytes);
+    pl.bytes[rt_prepared::W_CHILD] = slots * pl.nlev;
+    pl.bytes[rt_prepared::W_LIT] = slots * pl.nlev * sizeof(unsigned);
+    pl.bytes[rt_prepared::W_COUNTS] = max_tiles * pl.nlev * sizeof(int);
+    // dense work lists: 64 per-level record counts, then per level the slots of its records in tile order
+    pl.list0 = level_counts(pl.nlev);
+    pl.bytes[rt_prepared::W_ITEMS] = (pl.list0 + slots * pl.nlev) * sizeof(int);
+    if (hdr.beam_ok && D > 0) {
+        pl.slab_all = (int)f.slab_rows();
+        pl.nhalf = (size_t)pl.tiles_x * ((pl.slab_all + TILE - 1) / TILE) * 2;
+        pl.pmask_bytes = pl.nhalf * hdr.n_chunk * 8 + pl.nhalf; // after the masks: one byte per half-tile
     }
+    pl.lds = pl.lds_bvh = pl.staged ? (size_t)hdr.l_bytes : 0;
+    pl.rhdr = hdr;
+    if (pl.rhdr.bvh_ok) {
+        const size_t nb = (size_t)hdr.n_bvh * BVH_NODE_DOUBLES * 8, sb = (size_t)hdr.n_sph * SPH_W * 8;
+        if (nb + sb <= (size_t)BVH_LDS_MAX) {
+            pl.rhdr.l_bvh = (int)pl.lds_bvh;
+            pl.rhdr.l_bsph = (int)(pl.lds_bvh + nb);
+            pl.lds_bvh += nb + sb;
+        }
+        pl.rhdr.l_stack = (int)pl.lds_bvh;
+        pl.lds_bvh += (size_t)BLOCK * hdr.bvh_depth * sizeof(unsigned);
+    }
+    return pl;
+}
+
+// The work space of a plan's passes (grow bumps gen where it reallocates), and the side streams.
+int wave_grow(rt_prepared *p, const WavePlan &pl, int depth) {
+    for (int w = 0; w < rt_prepared::W_COUNT; ++w) {
+        const int rc = grow(p, (rt_prepared::Work)w, pl.bytes[w]);
+        if (rc != RT_OK) return rc;
+    }
+    return pl.overlap ? side_stream(p, depth) : RT_OK;
+}
+
+// The primary rays' candidate masks of the whole slab (k_pmask, on st), recomputed only when the
+// frame geometry — the raster's and the image's: two windows of one size at different origins see
+// different rays — or the scene changed (or after rt_trim).
+int wave_pmask(rt_prepared *p, const WavePlan &pl, const rt_frame &f, bool supersampled, hipStream_t st) {
+    if (!pl.pmask_bytes) return RT_OK;
+    const int W = (int)f.win.w, H = (int)f.win.h, rb = (int)f.row_block, sh = (int)f.shard, ns = (int)f.nshards;
+    const ImageGeom im = image_geom(f);
+    const long long key[12] = {W, H, rb, sh, ns, supersampled, (long long)p->scene_gen, pl.slab_all, im.IW, im.IH, im.x0, im.y0};
+    if (p->pmask_valid && std::memcmp(key, p->pmask_key, sizeof(key)) == 0) return RT_OK;
+    p->pmask_valid = false;
+    // New masks (and perhaps a new buffer): a frame graph captured with the old ones holds
+    // no k_pmask launch and would read these, so it is invalidated (gen).
+    ++p->gen;
+    const int rc = grow(p, rt_prepared::W_PMASK, pl.pmask_bytes);
+    if (rc != RT_OK) return rc;
+    const int nhalf = (int)pl.nhalf;
+    const dim3 pg((unsigned)std::min<size_t>(4096, (pl.nhalf + 3) / 4));
+    unsigned long long *const masks = p->buf<unsigned long long>(rt_prepared::W_PMASK);
+    KtScope kt(p, RT_KT_PMASK, st);
+    with_bool(supersampled, [&](auto ss) {
+        hipLaunchKernelGGL(k_pmask<decltype(ss)::value>, pg, dim3(256), 0, st, p->hdr, p->d_tab, p->d_itab, W, H, rb, sh,
+                           ns, pl.slab_all, nhalf, masks,
+                           reinterpret_cast<unsigned char *>(masks + pl.nhalf * p->hdr.n_chunk), im);
+    });
+    HIPCHK(hipGetLastError());
+    std::memcpy(p->pmask_key, key, sizeof(key));
+    p->pmask_valid = true;
     return RT_OK;
+}
+
+// The grid of a persistent per-level kernel: a wave per 64 slots of the pass's tiles, `cap` workgroups at most.
+int stride_blocks(int ntiles, int cap) {
+    return std::min<int>(cap, (ntiles * (TILE_SLOTS / 64) + BLOCK / 64 - 1) / (BLOCK / 64));
+}
+
+// One row pass: slab rows [row0, row0 + rows), its slices of the work space and its grids.
+struct WavePass {
+    hipStream_t st;
+    int rows, ntiles;
+    // the pass's first row of out / levels (the kernels map slab rows to image rows through the
+    // shard interleave themselves).  lv: the level count, null unless counted; lv0: k_primary's
+    void *o;
+    uint8_t *lv, *lv0;
+    PassGeom g; // level-0 records are rebuilt from it
+    HitRec *q;
+    double *colbuf;
+    double2 *terms; // the colour buffer as per-light terms (fold), else null
+    uint8_t *child;
+    unsigned *lit;
+    int *counts, *nitems, *lists; // nitems: [0, 64) per-level record counts
+    int sblocks, sblocks1, sblocksw, sblocksb;
+    size_t lslots() const { return (size_t)ntiles * TILE_SLOTS; } // record slots of one level
+    HitRec *qk(int k) const { return q + k * lslots(); }
+    int *ck(int k) const { return counts + (size_t)k * ntiles; }
+    int *ik(int k) const { return lists + k * lslots(); }
+    double *colk(int k) const { return k > 0 ? colbuf + (k - 1) * lslots() * COL_W : nullptr; }
+    uint8_t *chk(int k) const { return child + k * lslots(); }
+    unsigned *litk(int k) const { return lit + k * lslots(); }
+};
+
+// streams of the shading pass: level 0 (the bulk) beside the whole reflection chain, the next
+// levels each on their own, so no level waits for another's shading
+hipStream_t shade_stream(const rt_prepared *p, const WavePlan &pl, const WavePass &ps, int k) {
+    return pl.overlap ? p->side[std::min(k, 1)] : ps.st;
+}
+
+// level k's dense list, then its shading (k_light reads only level k: on a side stream it starts
+// as soon as the list exists and runs beside the next reflections)
+template <int PREC, bool GENPOW>
+int wave_level_lists(rt_prepared *p, const WavePlan &pl, const WavePass &ps, int k) {
+    // (inline walks: the deepest level is shaded by the launch that finds its hits, never queued)
+    if (pl.iw && k == pl.nrefl) return RT_OK;
+    const hipStream_t st = ps.st, ls = shade_stream(p, pl, ps, k);
+    const dim3 iblocks((ps.ntiles + ITEMS_BLOCK - 1) / ITEMS_BLOCK);
+    hipLaunchKernelGGL(k_items, iblocks, dim3(ITEMS_BLOCK), 0, st, ps.ck(k), ps.ntiles, ps.ik(k), ps.nitems + k);
+    HIPCHK(hipGetLastError());
+    if (pl.overlap) {
+        HIPCHK(hipEventRecord(p->ev_level[k], st));
+        HIPCHK(hipStreamWaitEvent(ls, p->ev_level[k], 0));
+    }
+    if (pl.fuse && k < pl.nrefl) return RT_OK; // shaded by k_reflect_shade(k + 1)
+    if (k == pl.nrefl && k >= 2) { // the deepest level >= 2: shaded by k_walk_deep / k_walk
+        if (pl.overlap) HIPCHK(hipEventRecord(p->ev_lit[k], ls));
+        return RT_OK;
+    }
+    // levels >= 2 are shaded here only when dense (decided on the device; otherwise the
+    // launch exits at once): a smaller persistent grid keeps the empty launch cheap
+    const int lblocks = k >= 2 ? std::min(ps.sblocks, DEEP_LIGHT_BLOCKS) : ps.sblocks;
+    with_sph(pl.staged, pl.sph_only, [&](auto sph) {
+        hipLaunchKernelGGL((k_light<PREC, GENPOW, decltype(sph)::value>), dim3(lblocks), dim3(BLOCK), pl.lds, ls, p->hdr,
+                           p->d_tab, p->d_itab, k, ps.o, ps.qk(k), ps.ik(k), ps.nitems + k, ps.colk(k), ps.litk(k), ps.g);
+    });
+    HIPCHK(hipGetLastError());
+    if (pl.overlap) HIPCHK(hipEventRecord(p->ev_lit[k], ls));
+    return RT_OK;
+}
+
+// The reflections of level k - 1's records into level k.  Level 1 (from the primary hits) is dense
+// and throughput-bound; deeper levels are a few waves each, bound by one wave's dependent chain:
+// they walk two candidates per step.
+template <int PREC, bool GENPOW>
+int wave_reflect(rt_prepared *p, const WavePlan &pl, const WavePass &ps, int k) {
+    const hipStream_t st = ps.st;
+    const bool iw = pl.iw;
+    const int nrefl = pl.nrefl;
+    if (pl.fuse) {
+        // levels traversing the sphere BVH (unstaged scenes only) take the BVH instantiations,
+        // the deepest level with inline walks the LAST ones; both only come with ILP
+        const bool bvh_k = pl.bvh_at(k), ilp = bvh_k || k != 1, last = ilp && iw && k == nrefl;
+        with_sph(pl.staged, pl.sph_only, [&](auto sph) {
+            constexpr int SPH = decltype(sph)::value;
+            auto rs = [&](auto ilp_c, auto bvh_c, auto last_c) {
+                constexpr bool BVH = decltype(bvh_c)::value;
+                hipLaunchKernelGGL(
+                    (k_reflect_shade<PREC, GENPOW, SPH, decltype(ilp_c)::value, BVH, decltype(last_c)::value>),
+                    dim3(k == 1 ? ps.sblocks1 : BVH ? ps.sblocksb : ps.sblocks), dim3(BLOCK), pl.lds_r(k), st, pl.rhdr,
+                    p->d_tab, p->d_itab, k, ps.o, ps.qk(k - 1), ps.ik(k - 1), ps.nitems + (k - 1), ps.qk(k), ps.ck(k),
+                    iw ? nullptr : ps.chk(k - 1), ps.colk(k - 1), ps.g, iw && k >= 2 ? (k == nrefl ? 2 : 1) : 0, ps.terms);
+            };
+            auto rs_ilp = [&](auto bvh_c) {
+                with_bool(last, [&](auto last_c) { rs(std::true_type{}, bvh_c, last_c); });
+            };
+            if (!ilp) rs(std::false_type{}, std::false_type{}, std::false_type{});
+            else if constexpr (SPH == 2) rs_ilp(std::false_type{}); // (staged: never the BVH, bvh_at)
+            else with_bool(bvh_k, rs_ilp);
+        });
+    } else {
+        with_bool(ps.lv != nullptr, [&](auto has_lv) {
+            with_bool(k != 1, [&](auto ilp_c) {
+                hipLaunchKernelGGL((k_reflect<decltype(has_lv)::value, decltype(ilp_c)::value>), dim3(ps.sblocks),
+                                   dim3(BLOCK), pl.lds, st, pl.rhdr, p->d_tab, p->d_itab, k, ps.qk(k - 1), ps.ik(k - 1),
+                                   ps.nitems + (k - 1), ps.qk(k), ps.ck(k), ps.lv, ps.chk(k - 1), ps.g);
+            });
+        });
+    }
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// The chain walks that finish a pass with reflections (nrefl > 0).  Without side streams one
+// k_walk finishes every chain (sparse deep levels shaded on the way).  With side streams (see
+// deep_dense): k_walk_deep right after the chain; the chains ending at level 1 (the bulk) are
+// finished on side stream 0 as soon as levels 0 and 1 are shaded, beside it; then the rest, once
+// every level's shading is in (side stream 1 shades levels 1.. in order: its last level's event
+// covers them all).
+template <int PREC, bool GENPOW>
+int wave_walks(rt_prepared *p, const WavePlan &pl, const WavePass &ps, int D) {
+    const SceneHdr &hdr = p->hdr;
+    const hipStream_t st = ps.st;
+    const bool overlap = pl.overlap, staged = pl.staged, sph_only = pl.sph_only;
+    const size_t ls_ = ps.lslots();
+    const bool bits = hdr.n_light <= 32; // the shadow answers fit the record
+    // deep: the merged walk (no k_walk_deep; without side streams); after k_reflect_shade
+    // (fuse) the shadow answers are in the children's records (PAD)
+    auto walk = [&](hipStream_t s_, int lo, int hi, bool deep) {
+        with_sph(staged, sph_only, [&](auto sph) {
+            with_bool(bits, [&](auto bits_c) {
+                auto launch = [&](auto deep_c, auto pad_c) {
+                    hipLaunchKernelGGL((k_walk<PREC, GENPOW, decltype(sph)::value, decltype(bits_c)::value,
+                                               decltype(deep_c)::value, decltype(pad_c)::value>),
+                                       dim3(ps.sblocksw), dim3(BLOCK), pl.lds, s_, hdr, p->d_tab, p->d_itab, D, ps.o, ps.q,
+                                       ls_, ps.lists, ps.nitems, ps.colbuf, ps.child, ps.lit, lo, hi, ps.g);
+                };
+                // (PAD is launched with DEEP and BITS only; its instantiations without BITS
+                // exist, as they always have, and are never run)
+                if (deep && pl.fuse && bits) launch(std::true_type{}, std::true_type{});
+                else if (deep) launch(std::true_type{}, std::false_type{});
+                else launch(std::false_type{}, std::false_type{});
+            });
+        });
+    };
+    if (overlap) { // side stream 0 (after level 0's shading) waits for level 1's, and for
+                   // k_reflect(2), which marks the level-1 records that have a child
+        HIPCHK(hipStreamWaitEvent(p->side[0], p->ev_lit[1], 0));
+        if (D > 2) HIPCHK(hipStreamWaitEvent(p->side[0], p->ev_level[2], 0));
+        walk(p->side[0], 1, 2, false);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(p->ev_lit[0], p->side[0]));
+    }
+    if (D > 2 && overlap) {
+        with_sph(staged, sph_only, [&](auto sph) {
+            hipLaunchKernelGGL((k_walk_deep<GENPOW, decltype(sph)::value>), dim3(ps.sblocks), dim3(BLOCK), pl.lds, st, hdr,
+                               p->d_tab, p->d_itab, D, ps.q, ls_, ps.lists, ps.nitems, ps.child, ps.colk(2));
+        });
+        HIPCHK(hipGetLastError());
+    }
+    if (overlap) {
+        HIPCHK(hipStreamWaitEvent(st, p->ev_lit[pl.nrefl], 0));
+        HIPCHK(hipStreamWaitEvent(st, p->ev_lit[0], 0));
+        if (D > 2) walk(st, 2, D, false);
+    } else if (!pl.iw) {
+        walk(st, 1, D, true); // every chain in one launch, sparse deep levels shaded there too
+    }
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// One row pass, slab rows [row0, ...) of the plan's range, enqueued on st: k_primary, then per
+// level the reflections and the lists (and what shades them), then the walks.  out / levels point
+// at slab row 0.
+template <int PREC, bool GENPOW>
+int wave_pass(rt_prepared *p, const WavePlan &pl, const rt_frame &f, int row0, void *out, uint8_t *levels,
+              hipStream_t st, const WaveSample &smp) {
+    const int W = (int)f.win.w, H = (int)f.win.h, D = (int)f.depth;
+    const int rb = (int)f.row_block, sh = (int)f.shard, ns = (int)f.nshards;
+    const ImageGeom im = image_geom(f);
+    WavePass ps = {};
+    ps.st = st;
+    ps.rows = std::min(pl.pass_rows, pl.row_end - row0);
+    const int ntiles = ps.ntiles = pl.tiles_x * ((ps.rows + TILE - 1) / TILE);
+    const size_t off = (size_t)row0 * W;
+    ps.o = static_cast<char *>(out) + off * 3 * (PREC == RT_OUT_F64 ? 8 : 4);
+    ps.lv0 = levels ? levels + off : nullptr;
+    ps.lv = pl.count_levels ? ps.lv0 : nullptr;
+    double *acc_p = smp.acc ? smp.acc + off * 3 : nullptr;
+    ps.q = p->buf<HitRec>(rt_prepared::W_QUEUE);
+    ps.colbuf = p->buf<double>(rt_prepared::W_COLBUF);
+    ps.terms = pl.fold ? reinterpret_cast<double2 *>(ps.colbuf) : nullptr;
+    ps.child = p->buf<uint8_t>(rt_prepared::W_CHILD);
+    ps.lit = p->buf<unsigned>(rt_prepared::W_LIT);
+    ps.counts = p->buf<int>(rt_prepared::W_COUNTS);
+    ps.nitems = p->buf<int>(rt_prepared::W_ITEMS);
+    ps.lists = ps.nitems + pl.list0;
+    ps.sblocks = stride_blocks(ntiles, STRIDE_BLOCKS);
+    ps.sblocks1 = stride_blocks(ntiles, STRIDE_BLOCKS_L1);
+    ps.sblocksw = stride_blocks(ntiles, STRIDE_BLOCKS_WALK);
+    ps.sblocksb = stride_blocks(ntiles, STRIDE_BLOCKS_BVH);
+    const unsigned long long *pmask = pl.pmask_bytes ? p->buf<unsigned long long>(rt_prepared::W_PMASK) : nullptr;
+    // after the masks: one byte per half-tile, 1 = every mask zero
+    const unsigned short *pempty =
+        pmask ? reinterpret_cast<const unsigned short *>(pmask + pl.nhalf * p->hdr.n_chunk) : nullptr;
+    const int sarg = sample_arg(smp.sample, smp.keep);
+    ps.g = make_pass_geom(W, im, rb, sh, ns, row0, smp.spp, sarg, smp.seed, acc_p);
+    const dim3 grid(std::min(ntiles, PRIMARY_GRID)); // k_primary: grid-stride loop over the tiles
+    {
+        KtScope kt(p, RT_KT_PRIMARY, st);
+        with_bool(ps.lv0 != nullptr, [&](auto has_lv) { // (without lv0 there is no lv either)
+            hipLaunchKernelGGL((k_primary<PREC, decltype(has_lv)::value>), grid, dim3(PRIMARY_BLOCK), 0, st, p->hdr,
+                               p->d_tab, p->d_itab, W, im.y0 + H, D, rb, ps.g.yoff, ns, ps.rows, row0, ps.o, ps.lv0, ps.q,
+                               ps.counts, ntiles, smp.spp, sarg, smp.seed, acc_p, pmask, pempty, ps.nitems, ps.g.img);
+        });
+    }
+    HIPCHK(hipGetLastError());
+    int rc = RT_OK;
+    if (pl.nshade > 0 && (rc = wave_level_lists<PREC, GENPOW>(p, pl, ps, 0)) != RT_OK) return rc;
+    for (int k = 1; k <= pl.nrefl; ++k) {
+        KtScope kt(p, k == 1 ? RT_KT_LEVEL1 : 0, st); // (level 1's time takes in its list and k_light)
+        if ((rc = wave_reflect<PREC, GENPOW>(p, pl, ps, k)) != RT_OK) return rc;
+        if ((rc = wave_level_lists<PREC, GENPOW>(p, pl, ps, k)) != RT_OK) return rc;
+    }
+    if (pl.nrefl > 0) return wave_walks<PREC, GENPOW>(p, pl, ps, D);
+    if (pl.overlap && pl.nshade > 0) HIPCHK(hipStreamWaitEvent(st, p->ev_lit[0], 0));
+    return RT_OK;
+}
+
+// The wavefront engine: slab rows [row_begin, row_end) of f (row_begin a multiple of TILE), in as
+// many row passes as the queue budget asks for; out / levels point at slab row 0.
+template <int PREC, bool GENPOW>
+int launch_wavefront(rt_prepared *p, const rt_frame &f, int row_begin, int row_end, void *out, uint8_t *levels,
+                     hipStream_t st, const WaveSample &smp) {
+    const WavePlan pl = wave_plan(p, f, row_begin, row_end, levels != nullptr, smp.levels_hit);
+    int rc = wave_grow(p, pl, (int)f.depth);
+    if (rc == RT_OK) rc = wave_pmask(p, pl, f, smp.spp > 1, st);
+    for (int row0 = row_begin; row0 < row_end && rc == RT_OK; row0 += pl.pass_rows)
+        rc = wave_pass<PREC, GENPOW>(p, pl, f, row0, out, levels, st, smp);
+    return rc;
 }
 
 // RT_GRAPH=1 enables frame graphs.  Off by default: measured on MI355X (ROCm 7), replaying
@@ -981,7 +1079,139 @@ bool use_mega_engine(const rt_prepared *p, int depth = 0, int order = RT_ORDER_E
     return h.n_obj <= FUSED_MAX_OBJECTS;
 }
 
+// One wavefront pass per sample of a band, summed in order: what rt_launch_rows (spp > 1) and
+// rt_launch_samples share.  Samples [s0, s1) of slab rows [r0, r1) of f are folded into acc (slab
+// row 0); sample 0 is the one that writes the levels.
+struct SampleBand {
+    uint32_t r0, r1, s0, s1;
+    double *acc;
+    // the frame of f.precision (slab row 0) that the pass of the last sample writes — or, with
+    // keep (RT_PROGRESSIVE), nothing: every pass only accumulates, and out is never written
+    void *out;
+    bool keep;
+};
+int launch_sample_passes(rt_prepared *p, const rt_frame &f, const SampleBand &b, uint8_t *d_levels, int levels_hit,
+                         hipStream_t st) {
+    // the band's rows inside the image (a prefix of the slab)
+    const size_t v1 = std::min<size_t>(f.valid_rows(), b.r1);
+    if (v1 <= b.r0) return RT_OK;
+    const size_t e0 = (size_t)b.r0 * f.win.w * 3, n = (v1 - b.r0) * f.win.w * 3; // the band's elements
+    const int blocks = (int)std::min<size_t>(8192, (n + 255) / 256);
+    for (uint32_t s = b.s0; s < b.s1; ++s) {
+        uint8_t *lv = s == 0 ? d_levels : nullptr;
+        WaveSample smp;
+        smp.sample = (int)s;
+        smp.spp = (int)f.spp;
+        smp.seed = f.seed;
+        smp.keep = b.keep;
+        smp.levels_hit = levels_hit;
+        // every pixel written once: the pass folds its sample into acc (and the last one writes the
+        // output) itself — no sample slab, no k_accum; otherwise a binary64 sample slab, then k_accum
+        const bool single = wave_plan(p, f, (int)b.r0, (int)b.r1, lv != nullptr, levels_hit).single_write();
+        double *slab = nullptr; // the pass's own slab, where it does not write every pixel exactly once
+        if (single) {
+            smp.acc = b.acc;
+        } else {
+            const int rc = grow(p, rt_prepared::W_SAMPLE, (size_t)f.slab_rows() * f.win.w * 3 * sizeof(double));
+            if (rc != RT_OK) return rc;
+            slab = p->buf<double>(rt_prepared::W_SAMPLE);
+        }
+        const int rc = with_prec_pow(single ? f.precision : RT_OUT_F64, p->hdr.int_pow, [&](auto prec, auto genpow) {
+            return launch_wavefront<decltype(prec)::value, decltype(genpow)::value>(
+                p, f, (int)b.r0, (int)b.r1, single ? b.out : slab, lv, st, smp);
+        });
+        if (rc != RT_OK) return rc;
+        if (single) continue;
+        // keep: k_accum told of a frame one sample longer folds and keeps the sum, and never reads its output
+        void *dst = b.keep ? nullptr : static_cast<char *>(b.out) + e0 * (f.precision == RT_OUT_F64 ? 8 : 4);
+        with_int<RT_OUT_F64, RT_OUT_F32>(f.precision, [&](auto prec) {
+            hipLaunchKernelGGL(k_accum<decltype(prec)::value>, dim3(blocks), dim3(256), 0, st, n, slab + e0, b.acc + e0, dst,
+                               (int)s, b.keep ? (int)s + 2 : (int)f.spp);
+        });
+        HIPCHK(hipGetLastError());
+    }
+    return RT_OK;
+}
+
+// The whole frame width x height as shard `shard`, binary64 in the reference's order, one sample:
+// what the exported launches start from.
+rt_frame whole_frame(uint32_t width, uint32_t height, uint32_t depth, uint32_t row_block, uint32_t shard,
+                     uint32_t nshards) {
+    rt_frame f = {};
+    f.img_w = width;
+    f.img_h = height;
+    f.win = rt_window{0, 0, width, height};
+    f.depth = depth;
+    f.row_block = row_block;
+    f.shard = shard;
+    f.nshards = nshards;
+    f.precision = RT_OUT_F64;
+    f.order = RT_ORDER_EXACT;
+    f.spp = 1;
+    return f;
+}
+
 } // namespace
+
+int rt_frame_check(const rt_frame &f) {
+    const rt_window &w = f.win;
+    if (f.img_w == 0 && f.img_h == 0 && w.w == 0 && w.h == 0 && w.x0 == 0 && w.y0 == 0) return RT_DONE;
+    if (f.img_w == 0 || f.img_h == 0) return RT_EBADARG;
+    if (f.row_block == 0 || f.nshards == 0 || f.shard >= f.nshards) return RT_EBADARG;
+    if (f.precision != RT_OUT_F64 && f.precision != RT_OUT_F32) return RT_EBADARG;
+    if (f.order != RT_ORDER_EXACT && f.order != RT_ORDER_FAST) return RT_EBADARG;
+    if (f.spp == 0) return RT_EBADARG;
+    if (f.spp > RT_MAX_SPP) return RT_ETOOBIG;
+    if (f.img_w > (1u << 20) || f.img_h > (1u << 20)) return RT_ETOOBIG;
+    // the window: not empty, inside the image (sums in 64 bits: x0 + w may pass 2^32)
+    if (w.w == 0 || w.h == 0) return RT_EBADARG;
+    if ((uint64_t)w.x0 + w.w > f.img_w || (uint64_t)w.y0 + w.h > f.img_h) return RT_EBADARG;
+    if ((uint64_t)f.slab_rows() > 65535ull * TILE) return RT_ETOOBIG;
+    return RT_OK;
+}
+
+// Slab rows [row_begin, min(row_end, slab rows)) of f: the boundary (rt_host.hip) renders a frame
+// in row bands so that each band's copy to the host overlaps the next band's render.  The kernels
+// tile and store the window; the image it lies in only places the rays.
+int rt_launch_rows(rt_prepared *p, const rt_frame &f, uint32_t row_begin, uint32_t row_end, void *d_out,
+                   uint8_t *d_levels, void *stream, int levels_hit) {
+    if (!p || !d_out) return RT_EBADARG;
+    const int ok = rt_frame_check(f);
+    if (ok != RT_OK) return ok;
+    const uint32_t slab = f.slab_rows();
+    if (row_begin % TILE) return RT_EBADARG;
+    if (row_end > slab) row_end = slab;
+    if (row_begin >= row_end) return RT_OK;
+    DevGuard g(p->device);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int r0 = (int)row_begin, r1 = (int)row_end;
+    if (f.spp > 1) { // RT_SUPERSAMPLING, on the wavefront engine: one sample's slab and the running sum
+        if (f.valid_rows() <= row_begin) return RT_OK;
+        const size_t n_slab = (size_t)slab * f.win.w * 3;
+        const int rc = grow(p, rt_prepared::W_SAMPLE, 2 * n_slab * sizeof(double));
+        if (rc != RT_OK) return rc;
+        const SampleBand b = {row_begin, row_end, 0, f.spp, p->buf<double>(rt_prepared::W_SAMPLE) + n_slab, d_out, false};
+        return launch_sample_passes(p, f, b, d_levels, levels_hit, st);
+    }
+    WaveSample one;
+    one.levels_hit = levels_hit;
+    if (!use_mega_engine(p, (int)f.depth, f.order)) { // the wavefront engine always evaluates the reference's exact order
+        const long long key[16] = {f.win.w, f.win.h, f.depth, f.row_block, f.shard, f.nshards, f.precision,
+                                   ((long long)r0 << 32) | r1, (long long)(intptr_t)d_out, (long long)(intptr_t)d_levels,
+                                   levels_hit, f.img_w, f.img_h, f.win.x0, f.win.y0, 0};
+        return launch_frame(p, key, st, [&](hipStream_t s) {
+            return with_prec_pow(f.precision, p->hdr.int_pow, [&](auto prec, auto genpow) {
+                return launch_wavefront<decltype(prec)::value, decltype(genpow)::value>(p, f, r0, r1, d_out, d_levels, s, one);
+            });
+        });
+    }
+    return with_int<RT_ORDER_EXACT, RT_ORDER_FAST>(f.order, [&](auto ord) {
+        return with_prec_pow(f.precision, p->hdr.int_pow, [&](auto prec, auto genpow) {
+            return launch_t<decltype(ord)::value, decltype(prec)::value, decltype(genpow)::value>(
+                p, f, r0, r1, d_out, d_levels, st, levels_hit);
+        });
+    });
+}
 
 extern "C" {
 
@@ -992,183 +1222,54 @@ int rt_engine(rt_prepared *p, uint32_t spp) {
 
 int rt_launch(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t row_block, uint32_t shard,
               uint32_t nshards, int precision, int order, void *d_out, uint8_t *d_levels, void *stream) {
-    return rt_launch_spp(p, width, height, depth, row_block, shard, nshards, precision, order, 1, 0, d_out, d_levels,
-                         stream);
+    rt_frame f = whole_frame(width, height, depth, row_block, shard, nshards);
+    f.precision = precision;
+    f.order = order;
+    return rt_launch_rows(p, f, 0, ~0u, d_out, d_levels, stream, 0);
 }
 
 int rt_launch_spp(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t row_block,
                   uint32_t shard, uint32_t nshards, int precision, int order, uint32_t spp, uint64_t seed,
                   void *d_out, uint8_t *d_levels, void *stream) {
-    return rt_launch_window(p, width, height, depth, 0, 0, width, height, row_block, shard, nshards, precision, order,
-                            spp, seed, d_out, d_levels, stream);
+    rt_frame f = whole_frame(width, height, depth, row_block, shard, nshards);
+    f.precision = precision;
+    f.order = order;
+    f.spp = spp;
+    f.seed = seed;
+    return rt_launch_rows(p, f, 0, ~0u, d_out, d_levels, stream, 0);
 }
 
 int rt_launch_window(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t x0, uint32_t y0,
                      uint32_t win_w, uint32_t win_h, uint32_t row_block, uint32_t shard, uint32_t nshards, int precision,
                      int order, uint32_t spp, uint64_t seed, void *d_out, uint8_t *d_levels, void *stream) {
-    return rt_launch_rows(p, width, height, depth, x0, y0, win_w, win_h, row_block, shard, nshards, precision, order, spp,
-                          seed, 0, ~0u, d_out, d_levels, stream, 0);
+    rt_frame f = whole_frame(width, height, depth, row_block, shard, nshards);
+    f.win = rt_window{x0, y0, win_w, win_h};
+    f.precision = precision;
+    f.order = order;
+    f.spp = spp;
+    f.seed = seed;
+    return rt_launch_rows(p, f, 0, ~0u, d_out, d_levels, stream, 0);
 }
-
-} // extern "C"
-
-namespace {
-
-// The size, shard and window checks of rt_launch_window and rt_launch_samples, in one place so that
-// they are the same: RT_OK, RT_DONE or an error; nothing is dereferenced and no HIP call is made.
-int launch_args_check(uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t win_w, uint32_t win_h,
-                      uint32_t row_block, uint32_t shard, uint32_t nshards, int precision, int order, uint32_t spp) {
-    if (width == 0 && height == 0 && win_w == 0 && win_h == 0 && x0 == 0 && y0 == 0) return RT_DONE;
-    if (width == 0 || height == 0) return RT_EBADARG;
-    if (row_block == 0 || nshards == 0 || shard >= nshards) return RT_EBADARG;
-    if (precision != RT_OUT_F64 && precision != RT_OUT_F32) return RT_EBADARG;
-    if (order != RT_ORDER_EXACT && order != RT_ORDER_FAST) return RT_EBADARG;
-    if (spp == 0) return RT_EBADARG;
-    if (spp > RT_MAX_SPP) return RT_ETOOBIG;
-    if (width > (1u << 20) || height > (1u << 20)) return RT_ETOOBIG;
-    // the window: not empty, inside the image (sums in 64 bits: x0 + win_w may pass 2^32)
-    if (win_w == 0 || win_h == 0) return RT_EBADARG;
-    if ((uint64_t)x0 + win_w > width || (uint64_t)y0 + win_h > height) return RT_EBADARG;
-    if ((uint64_t)rt_shard_rows(win_h, row_block, nshards) > 65535ull * TILE) return RT_ETOOBIG;
-    return RT_OK;
-}
-
-} // namespace
-
-// rt_launch_window restricted to slab rows [row_begin, min(row_end, slab rows)) of the window: the
-// boundary (rt_host.hip) renders a frame in row bands so that each band's copy to the host overlaps
-// the next band's render.  row_begin must be a multiple of 16 (the tile height).  From here on
-// (W, H) is the raster the kernels tile and store — the window — and `im` the image it lies in.
-int rt_launch_rows(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t x0, uint32_t y0,
-                   uint32_t win_w, uint32_t win_h, uint32_t row_block, uint32_t shard, uint32_t nshards, int precision,
-                   int order, uint32_t spp, uint64_t seed, uint32_t row_begin, uint32_t row_end, void *d_out,
-                   uint8_t *d_levels, void *stream, int levels_hit) {
-    if (!p || !d_out) return RT_EBADARG;
-    const int ok = launch_args_check(width, height, x0, y0, win_w, win_h, row_block, shard, nshards, precision, order, spp);
-    if (ok != RT_OK) return ok;
-    const ImageGeom im{(int)width, (int)height, (int)x0, (int)y0};
-    uint32_t slab = rt_shard_rows(win_h, row_block, nshards);
-    if (row_begin % TILE) return RT_EBADARG;
-    if (row_end > slab) row_end = slab;
-    if (row_begin >= row_end) return RT_OK;
-    DevGuard g(p->device);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int W = (int)win_w, H = (int)win_h, D = (int)depth, rb = (int)row_block, sh = (int)shard, ns = (int)nshards;
-    const int r0 = (int)row_begin, r1 = (int)row_end, slab_rows = (int)slab;
-    if (spp > 1) { // RT_SUPERSAMPLING, on the wavefront engine: one pass per sample, summed in order
-        // the slab rows inside the image (a prefix: global rows grow with slab rows)
-        const size_t valid_rows = valid_slab_rows(H, rb, sh, ns);
-        const size_t v1 = std::min<size_t>(valid_rows, (size_t)r1);
-        if (v1 <= (size_t)r0) return RT_OK;
-        const size_t e0 = (size_t)r0 * W * 3, n = (v1 - r0) * W * 3; // the band's elements
-        const size_t n_slab = (size_t)slab_rows * W * 3;
-        int rc = grow(p, rt_prepared::W_SAMPLE, 2 * n_slab * sizeof(double));
-        if (rc != RT_OK) return rc;
-        double *smp = p->buf<double>(rt_prepared::W_SAMPLE), *acc = smp + n_slab;
-        const int blocks = (int)std::min<size_t>(8192, (n + 255) / 256);
-        void *dst = static_cast<char *>(d_out) + e0 * (precision == RT_OUT_F64 ? 8 : 4);
-        for (int s = 0; s < (int)spp; ++s) {
-            uint8_t *lv = s == 0 ? d_levels : nullptr;
-            // every pixel written once: the pass folds its sample into acc (and the last one writes the
-            // output) itself — no sample slab, no k_accum; otherwise a binary64 sample slab, then k_accum
-            const bool single = wave_single_write(p, D, lv != nullptr && !levels_hit);
-            rc = with_prec_pow(single ? precision : RT_OUT_F64, p->hdr.int_pow, [&](auto prec, auto genpow) {
-                return launch_wavefront<decltype(prec)::value, decltype(genpow)::value>(
-                    p, W, H, im, D, rb, sh, ns, r0, r1, single ? d_out : smp, lv, st, (int)spp, s, seed,
-                    single ? acc : nullptr, levels_hit);
-            });
-            if (rc != RT_OK) return rc;
-            if (single) continue;
-            with_int<RT_OUT_F64, RT_OUT_F32>(precision, [&](auto prec) {
-                hipLaunchKernelGGL(k_accum<decltype(prec)::value>, dim3(blocks), dim3(256), 0, st, n, smp + e0, acc + e0, dst,
-                                   s, (int)spp);
-            });
-            HIPCHK(hipGetLastError());
-        }
-        return RT_OK;
-    }
-    if (!use_mega_engine(p, D, order)) { // the wavefront engine always evaluates the reference's exact order
-        const long long key[16] = {W, H, D, rb, sh, ns, precision, ((long long)r0 << 32) | r1,
-                                   (long long)(intptr_t)d_out, (long long)(intptr_t)d_levels, levels_hit,
-                                   im.IW, im.IH, im.x0, im.y0, 0};
-        return launch_frame(p, key, st, [&](hipStream_t s) {
-            return with_prec_pow(precision, p->hdr.int_pow, [&](auto prec, auto genpow) {
-                return launch_wavefront<decltype(prec)::value, decltype(genpow)::value>(
-                    p, W, H, im, D, rb, sh, ns, r0, r1, d_out, d_levels, s, 1, 0, 0, nullptr, levels_hit);
-            });
-        });
-    }
-    return with_int<RT_ORDER_EXACT, RT_ORDER_FAST>(order, [&](auto ord) {
-        return with_prec_pow(precision, p->hdr.int_pow, [&](auto prec, auto genpow) {
-            return launch_t<decltype(ord)::value, decltype(prec)::value, decltype(genpow)::value>(
-                p, W, H, im, D, rb, sh, ns, r0, r1, d_out, d_levels, st, levels_hit);
-        });
-    });
-}
-
-extern "C" {
 
 // RT_PROGRESSIVE: samples [sample_begin, sample_end) of rt_launch_window's frame folded into the
 // caller's binary64 sum, one wavefront pass per sample with rt_launch_rows' choice between the two
-// ways of summing.  Every pass has the keep bit: none divides, none writes a frame.
+// ways of summing.  Every pass has the keep bit: none divides, none writes a frame (a single-write
+// pass is handed the sum as its frame too: it stores to neither).
 int rt_launch_samples(rt_prepared *p, uint32_t width, uint32_t height, uint32_t depth, uint32_t x0, uint32_t y0,
                       uint32_t win_w, uint32_t win_h, uint32_t row_block, uint32_t shard, uint32_t nshards, uint32_t spp,
                       uint64_t seed, uint32_t sample_begin, uint32_t sample_end, double *d_sum, uint8_t *d_levels,
                       void *stream) {
     if (!p || !d_sum || (uintptr_t)d_sum % 8) return RT_EBADARG;
-    const int ok = launch_args_check(width, height, x0, y0, win_w, win_h, row_block, shard, nshards, RT_OUT_F64,
-                                     RT_ORDER_EXACT, spp);
+    rt_frame f = whole_frame(width, height, depth, row_block, shard, nshards);
+    f.win = rt_window{x0, y0, win_w, win_h};
+    f.spp = spp;
+    f.seed = seed;
+    const int ok = rt_frame_check(f);
     if (ok != RT_OK) return ok;
     if (sample_begin >= sample_end || sample_end > spp) return RT_EBADARG;
-    const ImageGeom im{(int)width, (int)height, (int)x0, (int)y0};
     DevGuard g(p->device);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int W = (int)win_w, H = (int)win_h, D = (int)depth, rb = (int)row_block, sh = (int)shard, ns = (int)nshards;
-    const int slab_rows = (int)rt_shard_rows(win_h, row_block, nshards);
-    const size_t n = valid_slab_rows(H, rb, sh, ns) * W * 3; // the slab's elements inside the image, a prefix
-    if (n == 0) return RT_OK;
-    const int blocks = (int)std::min<size_t>(8192, (n + 255) / 256);
-    for (uint32_t s = sample_begin; s < sample_end; ++s) {
-        uint8_t *lv = s == 0 ? d_levels : nullptr;
-        const bool single = wave_single_write(p, D, lv != nullptr);
-        double *smp = nullptr; // the pass's own slab, where it does not write every pixel exactly once
-        if (!single) {
-            const int rc = grow(p, rt_prepared::W_SAMPLE, (size_t)slab_rows * W * 3 * sizeof(double));
-            if (rc != RT_OK) return rc;
-            smp = p->buf<double>(rt_prepared::W_SAMPLE);
-        }
-        // (a single-write pass is handed the sum as its frame too: with the keep bit it stores to neither)
-        const int rc = with_bool(!p->hdr.int_pow, [&](auto genpow) {
-            return launch_wavefront<RT_OUT_F64, decltype(genpow)::value>(p, W, H, im, D, rb, sh, ns, 0, slab_rows,
-                                                                         single ? d_sum : smp, lv, st, (int)spp, (int)s,
-                                                                         seed, single ? d_sum : nullptr, 0, true);
-        });
-        if (rc != RT_OK) return rc;
-        if (single) continue;
-        // k_accum told of a frame one sample longer: it folds and keeps the sum, and never reads `out`
-        hipLaunchKernelGGL(k_accum<RT_OUT_F64>, dim3(blocks), dim3(256), 0, st, n, smp, d_sum, nullptr, (int)s,
-                           (int)s + 2);
-        HIPCHK(hipGetLastError());
-    }
-    return RT_OK;
-}
-
-// Copy the blocks of one shard's slab to their rows in a row-major image.  dst_kind selects
-// hipMemcpyDeviceToDevice or DeviceToHost.
-static int scatter_slab(const char *slab, uint32_t rowbytes, uint32_t H, uint32_t rb, uint32_t shard,
-                        uint32_t nshards, char *image, hipMemcpyKind kind, hipStream_t st) {
-    uint64_t blk_bytes = (uint64_t)rb * rowbytes;
-    uint32_t nfull = 0;
-    while ((((uint64_t)nfull * nshards + shard) * rb + rb) <= H) nfull++;
-    if (nfull)
-        HIPCHK(hipMemcpy2DAsync(image + (uint64_t)shard * blk_bytes, (size_t)blk_bytes * nshards, slab,
-                                (size_t)blk_bytes, (size_t)blk_bytes, nfull, kind, st));
-    uint64_t g0 = ((uint64_t)nfull * nshards + shard) * rb;
-    if (g0 < H) { // one partial block at the bottom of the image
-        uint64_t rows = H - g0;
-        HIPCHK(hipMemcpyAsync(image + g0 * rowbytes, slab + (uint64_t)nfull * blk_bytes, rows * rowbytes, kind, st));
-    }
-    return RT_OK;
+    const SampleBand b = {0, f.slab_rows(), sample_begin, sample_end, d_sum, d_sum, true};
+    return launch_sample_passes(p, f, b, d_levels, 0, reinterpret_cast<hipStream_t>(stream));
 }
 
 int rt_unshard(const void *d_slabs, uint32_t width, uint32_t height, uint32_t row_block, uint32_t nshards,
@@ -1178,11 +1279,13 @@ int rt_unshard(const void *d_slabs, uint32_t width, uint32_t height, uint32_t ro
         return RT_EBADARG;
     uint32_t esz = precision == RT_OUT_F64 ? 8 : precision == RT_OUT_F32 ? 4 : precision == RT_OUT_U16 ? 2 : 1;
     uint32_t rowbytes = width * 3 * esz;
-    uint64_t slab_bytes = (uint64_t)rt_shard_rows(height, row_block, nshards) * rowbytes;
+    const uint32_t slab = rt_shard_slab_rows(height, row_block, nshards);
+    uint64_t slab_bytes = (uint64_t)slab * rowbytes;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     for (uint32_t s = 0; s < nshards; s++) {
-        int rc = scatter_slab(static_cast<const char *>(d_slabs) + s * slab_bytes, rowbytes, height, row_block, s,
-                              nshards, static_cast<char *>(d_image), hipMemcpyDeviceToDevice, st);
+        int rc = rt_scatter_rows_async(static_cast<const char *>(d_slabs) + s * slab_bytes, 0, slab, rowbytes,
+                                       rt_shard_map{height, row_block, s, nshards}, static_cast<char *>(d_image),
+                                       hipMemcpyDeviceToDevice, st);
         if (rc != RT_OK) return rc;
     }
     return RT_OK;

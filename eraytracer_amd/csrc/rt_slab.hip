@@ -32,6 +32,7 @@
 #include <cstdio>
 
 #include "../../include/rt_mi355x.h"
+#include "rt_shard.h"
 
 namespace {
 
@@ -61,17 +62,6 @@ __host__ __device__ inline Layout layout(uint32_t width, uint32_t rows) {
     l.mask_at = (HDR_OFFS + l.nblk * 4 + 255) / 256 * 256;
     l.bytes = l.mask_at + l.nblk * (SLAB_BLOCK / 8);
     return l;
-}
-
-// slab rows inside the image: a prefix of the slab (rt_launch's interleave)
-uint64_t valid_rows(uint32_t height, uint32_t rb, uint32_t shard, uint32_t ns, uint32_t rows) {
-    uint64_t n = 0;
-    for (uint64_t b = 0; b * rb < rows; ++b) {
-        const uint64_t g0 = (b * ns + shard) * rb;
-        if (g0 >= height) break;
-        n += (g0 + rb <= height) ? rb : height - g0;
-    }
-    return n;
 }
 
 template <typename T>
@@ -471,8 +461,8 @@ int rt_slab_pack(const void *d_slab, uint32_t width, uint32_t height, uint32_t r
     uint32_t *off = reinterpret_cast<uint32_t *>(h + HDR_OFFS);
     uint64_t *mask = reinterpret_cast<uint64_t *>(h + l.mask_at);
     const dim3 grid((unsigned)l.nblk), blk(SLAB_BLOCK);
-    const uint64_t valid_px =
-        valid_rows(height, row_block, shard, nshards, rt_shard_rows(height, row_block, nshards)) * width;
+    // the slab rows inside the image are a prefix of the slab (rt_shard.h)
+    const uint64_t valid_px = (uint64_t)rt_shard_valid_rows(height, row_block, shard, nshards) * width;
     if (is_int(precision))
         return precision == RT_OUT_U8 ? pack_int<uint8_t>(d_slab, l, valid_px, h, d_values, st)
                                       : pack_int<uint16_t>(d_slab, l, valid_px, h, d_values, st);

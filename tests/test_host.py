@@ -129,3 +129,23 @@ def test_scene_compiler_under_host_sanitizers(tmp_path):
     assert len(rows) == len(files)
     for row in rows[:len(scenes_)]:
         assert row[0] == "0" and row[2] == "0", row  # valid scenes compile
+
+
+def test_shard_mapping_under_host_sanitizers(tmp_path):
+    """The host side's one copy of the shard interleave (rt_shard.h), built with AddressSanitizer +
+    UBSan: for every H in 1..70, row block in {1, 2, 3, 5, 16, 17}, 1..5 shards and every shard, the
+    closed-form valid row count equals the block-by-block sum, a slab row lies inside the image
+    exactly when it is below that count (the prefix property), and over all shards every image row is
+    hit once (tests/csrc/shard_check.cpp)."""
+    import shutil
+    import subprocess
+
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "shard_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(root, "tests", "csrc", "shard_check.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    assert int(r.stdout) == 70 * 6 * (1 + 2 + 3 + 4 + 5)  # every geometry was checked
