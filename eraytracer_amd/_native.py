@@ -165,6 +165,8 @@ def lib() -> ctypes.CDLL:
     L.rt_engine.argtypes = [vp, u32]
     L.rt_selftest_math.argtypes = [i32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     L.rt_eval_math.argtypes = [i32, i32, ctypes.c_uint64, vp, vp, vp, ctypes.c_int32, vp]
+    # test-only, not in the header (hence not in EXPORTS): the launch record, see launched() below
+    L.rt_debug_launched.argtypes = [vp, ctypes.c_char_p, i32, i32]
     L.rt_slab_header_bytes.restype = ctypes.c_size_t
     L.rt_slab_header_bytes.argtypes = [u32, u32, u32, u32]
     L.rt_slab_pack.argtypes = [vp, u32, u32, u32, u32, u32, i32, vp, vp, vp]
@@ -186,6 +188,17 @@ def check(code: int, what: str = "") -> int:
     if code < 0:
         raise RtError(code, what)
     return code
+
+
+def launched(p, reset: bool = False) -> frozenset:
+    """The kernel instantiations launched on context ``p`` since the last reset, each spelled as the
+    demangled name of its host stub (``k_walk<1, true, 2, true, true, false>``): the record that
+    tests/dispatch_matrix.py's table is checked against."""
+    buf = ctypes.create_string_buffer(1 << 15)  # (195 names of at most 60 characters)
+    need = check(lib().rt_debug_launched(p, buf, len(buf), int(reset)), "rt_debug_launched")
+    if need > len(buf):
+        raise RuntimeError(f"rt_debug_launched needs {need} bytes")
+    return frozenset(buf.value.decode().splitlines())
 
 
 class _Pinned:

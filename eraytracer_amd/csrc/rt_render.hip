@@ -43,6 +43,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <initializer_list>
 #include <mutex>
 #include <type_traits>
 #include <vector>
@@ -72,6 +73,39 @@ constexpr int TILE = 16;
 #include "rt_selftest.inc" // the arithmetic self-test kernels
 
 } // namespace
+
+// The launch record: which instantiation of each render-path kernel a context has launched (enqueued,
+// so a replayed frame graph adds nothing), for tests/dispatch_matrix.py.  A launch site ORs one bit
+// into its family's set; the bit is the template arguments read as the digits of a mixed-radix number
+// (an int argument ranges over [0, radix), a bool over false, true).  rt_debug_launched spells the set
+// bits as the demangled names of the kernels' host stubs.
+struct LaunchRecord {
+    enum Family { RENDER, PMASK, PRIMARY, ITEMS, REFLECT, REFLECT_SHADE, LIGHT, WALK, WALK_DEEP, ACCUM, NFAMILY };
+    static constexpr int MAX_ARGS = 6;
+    struct Spec {
+        const char *name;
+        int nargs;
+        int radix[MAX_ARGS]; // > 0: an int argument; -2: a bool
+    };
+    static constexpr Spec spec[NFAMILY] = {
+        {"k_render", 5, {2, 2, -2, -2, -2}},            // ORDER, PREC, LEVELS, GENPOW, NB
+        {"k_pmask", 1, {-2}},                           // JITTER
+        {"k_primary", 2, {2, -2}},                      // PREC, LEVELS
+        {"k_items", 0, {}},                             // (no template)
+        {"k_reflect", 2, {-2, -2}},                     // LEVELS, ILP
+        {"k_reflect_shade", 6, {2, -2, 3, -2, -2, -2}}, // PREC, GENPOW, SPH, ILP, BVH, LAST
+        {"k_light", 3, {2, -2, 3}},                     // PREC, GENPOW, SPH
+        {"k_walk", 6, {2, -2, 3, -2, -2, -2}},          // PREC, GENPOW, SPH, BITS, DEEP, PAD
+        {"k_walk_deep", 2, {-2, 3}},                    // GENPOW, SPH
+        {"k_accum", 1, {2}},                            // PREC
+    }; // (tests/test_dispatch_matrix.py reads this table and compares it with the compiled stubs)
+    unsigned long long bits[NFAMILY][2] = {}; // (the widest families have 96 instantiations)
+    void note(Family f, std::initializer_list<int> args) {
+        int i = 0, k = 0;
+        for (int a : args) i = i * std::abs(spec[f].radix[k++]) + a;
+        bits[f][i >> 6] |= 1ull << (i & 63);
+    }
+};
 
 // =====================================================================================
 // C ABI
@@ -141,6 +175,7 @@ struct rt_prepared {
     long long gkey[16] = {};
     long long last_key[16] = {};
     bool last_valid = false;
+    LaunchRecord launched; // rt_debug_launched
 };
 
 #define HIPCHK(x)                                                                                                  \
@@ -308,6 +343,7 @@ int launch_t(rt_prepared *p, const rt_frame &f, int row0, int row_end, void *out
     // scenes without wave beams (few spheres, e.g. the reference's own scene) take the beam-free build
     with_bool(levels != nullptr, [&](auto lv) {
         with_bool(!p->hdr.beam_ok, [&](auto nb) {
+            p->launched.note(LaunchRecord::RENDER, {ORDER, PREC, decltype(lv)::value, GENPOW, decltype(nb)::value});
             hipLaunchKernelGGL((k_render<ORDER, PREC, decltype(lv)::value, GENPOW, decltype(nb)::value>), grid,
                                dim3(BLOCK), lds, st, p->hdr, p->d_tab, p->d_itab, W, H, depth, rb, shard, nshards, row0,
                                row_end, out, levels, levels_hit, im.IW, im.IH, im.x0, im.y0);
@@ -334,6 +370,42 @@ int rt_debug_stats(unsigned long long *out, int n, int reset) {
     return RT_OK;
 }
 #endif
+
+// Test-only (not part of include/rt_mi355x.h; tests/dispatch_matrix.py): the kernel instantiations
+// launched on p since the last reset, one per line as the demangled name of its host stub
+// ("k_walk<1, true, 2, true, true, false>"), NUL-terminated, in buf[0, cap).  Returns the bytes the
+// whole text needs, the NUL included (text cut to cap when larger); reset != 0 then clears the record.
+int rt_debug_launched(rt_prepared *p, char *buf, int cap, int reset) {
+    if (!p || cap < 0 || (cap > 0 && !buf)) return RT_EBADARG;
+    size_t need = 0;
+    auto put = [&](const char *s) {
+        for (; *s; ++s, ++need)
+            if ((long long)need < (long long)cap - 1) buf[need] = *s;
+    };
+    for (int f = 0; f < LaunchRecord::NFAMILY; ++f) {
+        const LaunchRecord::Spec &sp = LaunchRecord::spec[f];
+        for (int i = 0; i < 128; ++i) {
+            if (!(p->launched.bits[f][i >> 6] >> (i & 63) & 1)) continue;
+            int digit[LaunchRecord::MAX_ARGS] = {};
+            for (int k = sp.nargs - 1, r = i; k >= 0; --k) {
+                const int radix = std::abs(sp.radix[k]);
+                digit[k] = r % radix;
+                r /= radix;
+            }
+            put(sp.name);
+            for (int k = 0; k < sp.nargs; ++k) {
+                char num[16];
+                std::snprintf(num, sizeof(num), "%d", digit[k]);
+                put(k ? ", " : "<");
+                put(sp.radix[k] > 0 ? num : digit[k] ? "true" : "false");
+            }
+            put(sp.nargs ? ">\n" : "\n");
+        }
+    }
+    if (cap > 0) buf[std::min<size_t>(need, (size_t)cap - 1)] = 0;
+    if (reset) p->launched = LaunchRecord{};
+    return (int)need + 1;
+}
 
 int rt_abi_version(void) { return RT_ABI_VERSION; }
 
@@ -736,6 +808,7 @@ int wave_pmask(rt_prepared *p, const WavePlan &pl, const rt_frame &f, bool super
     unsigned long long *const masks = p->buf<unsigned long long>(rt_prepared::W_PMASK);
     KtScope kt(p, RT_KT_PMASK, st);
     with_bool(supersampled, [&](auto ss) {
+        p->launched.note(LaunchRecord::PMASK, {decltype(ss)::value});
         hipLaunchKernelGGL(k_pmask<decltype(ss)::value>, pg, dim3(256), 0, st, p->hdr, p->d_tab, p->d_itab, W, H, rb, sh,
                            ns, pl.slab_all, nhalf, masks,
                            reinterpret_cast<unsigned char *>(masks + pl.nhalf * p->hdr.n_chunk), im);
@@ -790,6 +863,7 @@ int wave_level_lists(rt_prepared *p, const WavePlan &pl, const WavePass &ps, int
     if (pl.iw && k == pl.nrefl) return RT_OK;
     const hipStream_t st = ps.st, ls = shade_stream(p, pl, ps, k);
     const dim3 iblocks((ps.ntiles + ITEMS_BLOCK - 1) / ITEMS_BLOCK);
+    p->launched.note(LaunchRecord::ITEMS, {});
     hipLaunchKernelGGL(k_items, iblocks, dim3(ITEMS_BLOCK), 0, st, ps.ck(k), ps.ntiles, ps.ik(k), ps.nitems + k);
     HIPCHK(hipGetLastError());
     if (pl.overlap) {
@@ -805,6 +879,7 @@ int wave_level_lists(rt_prepared *p, const WavePlan &pl, const WavePass &ps, int
     // launch exits at once): a smaller persistent grid keeps the empty launch cheap
     const int lblocks = k >= 2 ? std::min(ps.sblocks, DEEP_LIGHT_BLOCKS) : ps.sblocks;
     with_sph(pl.staged, pl.sph_only, [&](auto sph) {
+        p->launched.note(LaunchRecord::LIGHT, {PREC, GENPOW, decltype(sph)::value});
         hipLaunchKernelGGL((k_light<PREC, GENPOW, decltype(sph)::value>), dim3(lblocks), dim3(BLOCK), pl.lds, ls, p->hdr,
                            p->d_tab, p->d_itab, k, ps.o, ps.qk(k), ps.ik(k), ps.nitems + k, ps.colk(k), ps.litk(k), ps.g);
     });
@@ -829,6 +904,8 @@ int wave_reflect(rt_prepared *p, const WavePlan &pl, const WavePass &ps, int k) 
             constexpr int SPH = decltype(sph)::value;
             auto rs = [&](auto ilp_c, auto bvh_c, auto last_c) {
                 constexpr bool BVH = decltype(bvh_c)::value;
+                p->launched.note(LaunchRecord::REFLECT_SHADE,
+                                 {PREC, GENPOW, SPH, decltype(ilp_c)::value, BVH, decltype(last_c)::value});
                 hipLaunchKernelGGL(
                     (k_reflect_shade<PREC, GENPOW, SPH, decltype(ilp_c)::value, BVH, decltype(last_c)::value>),
                     dim3(k == 1 ? ps.sblocks1 : BVH ? ps.sblocksb : ps.sblocks), dim3(BLOCK), pl.lds_r(k), st, pl.rhdr,
@@ -845,6 +922,7 @@ int wave_reflect(rt_prepared *p, const WavePlan &pl, const WavePass &ps, int k) 
     } else {
         with_bool(ps.lv != nullptr, [&](auto has_lv) {
             with_bool(k != 1, [&](auto ilp_c) {
+                p->launched.note(LaunchRecord::REFLECT, {decltype(has_lv)::value, decltype(ilp_c)::value});
                 hipLaunchKernelGGL((k_reflect<decltype(has_lv)::value, decltype(ilp_c)::value>), dim3(ps.sblocks),
                                    dim3(BLOCK), pl.lds, st, pl.rhdr, p->d_tab, p->d_itab, k, ps.qk(k - 1), ps.ik(k - 1),
                                    ps.nitems + (k - 1), ps.qk(k), ps.ck(k), ps.lv, ps.chk(k - 1), ps.g);
@@ -874,13 +952,16 @@ int wave_walks(rt_prepared *p, const WavePlan &pl, const WavePass &ps, int D) {
         with_sph(staged, sph_only, [&](auto sph) {
             with_bool(bits, [&](auto bits_c) {
                 auto launch = [&](auto deep_c, auto pad_c) {
+                    p->launched.note(LaunchRecord::WALK, {PREC, GENPOW, decltype(sph)::value, decltype(bits_c)::value,
+                                                          decltype(deep_c)::value, decltype(pad_c)::value});
                     hipLaunchKernelGGL((k_walk<PREC, GENPOW, decltype(sph)::value, decltype(bits_c)::value,
                                                decltype(deep_c)::value, decltype(pad_c)::value>),
                                        dim3(ps.sblocksw), dim3(BLOCK), pl.lds, s_, hdr, p->d_tab, p->d_itab, D, ps.o, ps.q,
                                        ls_, ps.lists, ps.nitems, ps.colbuf, ps.child, ps.lit, lo, hi, ps.g);
                 };
                 // (PAD is launched with DEEP and BITS only; its instantiations without BITS
-                // exist, as they always have, and are never run)
+                // exist, as they always have, and are never run: tests/dispatch_matrix.py lists
+                // them, with every other instantiation and the test that runs it)
                 if (deep && pl.fuse && bits) launch(std::true_type{}, std::true_type{});
                 else if (deep) launch(std::true_type{}, std::false_type{});
                 else launch(std::false_type{}, std::false_type{});
@@ -897,6 +978,7 @@ int wave_walks(rt_prepared *p, const WavePlan &pl, const WavePass &ps, int D) {
     }
     if (D > 2 && overlap) {
         with_sph(staged, sph_only, [&](auto sph) {
+            p->launched.note(LaunchRecord::WALK_DEEP, {GENPOW, decltype(sph)::value});
             hipLaunchKernelGGL((k_walk_deep<GENPOW, decltype(sph)::value>), dim3(ps.sblocks), dim3(BLOCK), pl.lds, st, hdr,
                                p->d_tab, p->d_itab, D, ps.q, ls_, ps.lists, ps.nitems, ps.child, ps.colk(2));
         });
@@ -953,6 +1035,7 @@ int wave_pass(rt_prepared *p, const WavePlan &pl, const rt_frame &f, int row0, v
     {
         KtScope kt(p, RT_KT_PRIMARY, st);
         with_bool(ps.lv0 != nullptr, [&](auto has_lv) { // (without lv0 there is no lv either)
+            p->launched.note(LaunchRecord::PRIMARY, {PREC, decltype(has_lv)::value});
             hipLaunchKernelGGL((k_primary<PREC, decltype(has_lv)::value>), grid, dim3(PRIMARY_BLOCK), 0, st, p->hdr,
                                p->d_tab, p->d_itab, W, im.y0 + H, D, rb, ps.g.yoff, ns, ps.rows, row0, ps.o, ps.lv0, ps.q,
                                ps.counts, ntiles, smp.spp, sarg, smp.seed, acc_p, pmask, pempty, ps.nitems, ps.g.img);
@@ -1125,6 +1208,7 @@ int launch_sample_passes(rt_prepared *p, const rt_frame &f, const SampleBand &b,
         // keep: k_accum told of a frame one sample longer folds and keeps the sum, and never reads its output
         void *dst = b.keep ? nullptr : static_cast<char *>(b.out) + e0 * (f.precision == RT_OUT_F64 ? 8 : 4);
         with_int<RT_OUT_F64, RT_OUT_F32>(f.precision, [&](auto prec) {
+            p->launched.note(LaunchRecord::ACCUM, {decltype(prec)::value});
             hipLaunchKernelGGL(k_accum<decltype(prec)::value>, dim3(blocks), dim3(256), 0, st, n, slab + e0, b.acc + e0, dst,
                                (int)s, b.keep ? (int)s + 2 : (int)f.spp);
         });

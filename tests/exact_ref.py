@@ -100,6 +100,24 @@ def exact_sqrt(x):
     return round_scaled(r, (e - k) // 2, sticky=r * r != M)
 
 
+def exact_pow_half(x, k):
+    """The correctly rounded x**(k/2) for a finite x >= 0 and an odd k >= 1 (k = 1: sqrt(x); k = 5:
+    x^2 sqrt(x) = x**2.5): the integer square root of m^k scaled, plus a sticky bit."""
+    k = int(k)
+    if k < 1 or not (k & 1) or not (x >= 0.0) or math.isinf(x):
+        raise ValueError(f"exact_pow_half({x!r}, {k!r})")
+    if x == 0.0:
+        return 0.0
+    m, e = _decompose(x)
+    M, E = m ** k, e * k
+    s = 2 * (MANT + 6)                      # M * 2**s >= 2**118: the root has at least 59 bits
+    if (E - s) & 1:                         # the exponent left over must be even
+        s += 1
+    M <<= s
+    r = math.isqrt(M)
+    return round_scaled(r, (E - s) // 2, sticky=r * r != M)
+
+
 def exact_div(a, b):
     """The correctly rounded a / b for finite a >= 0, b > 0 (integer quotient plus a sticky bit)."""
     if a == 0.0:

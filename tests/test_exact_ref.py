@@ -58,6 +58,26 @@ def test_exact_pow_against_fractions():
     assert np.array_equal(X.exact_pow_array(xs, ns), np.array([X.exact_pow(x, n) for x, n in ops]))
 
 
+def test_exact_pow_half_against_fractions():
+    """x**0.5 is the host's (correctly rounded) sqrt; x**2.5 lies between the squares of the midpoints
+    to its result's neighbours, exactly (fractions), down into the subnormal results."""
+    rnd = random.Random(0xE7)
+    xs = [rnd.random() for _ in range(1500)] + [2.0 ** (-430.0 * rnd.random()) for _ in range(1500)] + list(EDGE_X)
+    for x in xs:
+        assert X.exact_pow_half(x, 1) == math.sqrt(x) == X.exact_sqrt(x), x
+        got = X.exact_pow_half(x, 5)
+        true_sq = Fraction(x) ** 5
+        if got == 0.0:
+            assert true_sq <= Fraction(2.0 ** -1074) ** 2 / 4, x
+            continue
+        lo = (Fraction(got) + Fraction(math.nextafter(got, 0.0))) / 2
+        hi = (Fraction(got) + Fraction(math.nextafter(got, math.inf))) / 2
+        assert lo * lo <= true_sq <= hi * hi, (x, got)
+    assert X.exact_pow_half(4.0, 5) == 32.0 and X.exact_pow_half(0.25, 1) == 0.5 and X.exact_pow_half(1.0, 5) == 1.0
+    with pytest.raises(ValueError):
+        X.exact_pow_half(2.0, 4)
+
+
 def test_exact_pow_edges():
     assert X.exact_pow(0.0, 0) == 1.0 and X.exact_pow(0.0, 5) == 0.0 and X.exact_pow(1.0, 1024) == 1.0
     assert X.exact_pow(0.5, 1074) == 2.0 ** -1074

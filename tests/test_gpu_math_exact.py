@@ -134,6 +134,114 @@ def test_pow_inactive_lanes_carry_other_exponents(pow_set):
     report_pow("inactive lanes", got, want, sel=act.ravel() != 0)
 
 
+# ---- 1b. pow_libm<true> with the exponents mixed inside a wave --------------------------------
+# A general-power scene's waves hold lanes that leave pow_libm<true> through the device's pow()
+# (exponents that are no integer in 0..1024) beside lanes that take the binary powering, whose
+# wave-uniform check (__ballot / readlane) then runs on the narrowed exec mask.
+BIN_EXPONENTS = (0, 1, 4, 20, 1024)
+LIB_EXPONENTS = (0.5, 2.5, 1025)
+# HIP documents pow() in binary64 as within 1 ulp of the correctly rounded result
+LIB_POW_ULPS = 1
+
+
+@pytest.fixture(scope="module")
+def mixed_wave_set():
+    """(x, y, what) per wave of 64, x in [0, 1] (uniform, aimed at results over [2**-1080, 1] for each
+    lane's exponent, and the edge x), the exponents dealt per lane:
+      dealt        all eight exponents at random (32 waves)
+      one_bin      exactly one lane on the binary powering (lane 0, 63, two random), every BIN exponent
+      one_lib      exactly one lane through pow() (lane 0, 63, two random), every LIB exponent; the other
+                   lanes share one BIN exponent (the scalar-controlled powering) or hold all five
+      lib_lane0    lane 0 (readlane's fall-back) and a random third of the others through pow()
+      lib_half     lanes 0..31 through pow(), lanes 32..63 one BIN exponent; and the other way round
+      all_lib      no lane left for the binary powering"""
+    rng = np.random.default_rng(0x5EED9B)
+    lane = np.arange(64)
+    waves = []
+
+    def add(what, y):
+        waves.append((what, np.asarray(y, dtype=np.float64)))
+
+    for _ in range(32):
+        add("dealt", rng.choice(BIN_EXPONENTS + LIB_EXPONENTS, 64))
+    for n in BIN_EXPONENTS:
+        for at in (0, 63, int(rng.integers(1, 63)), int(rng.integers(1, 63))):
+            y = rng.choice(LIB_EXPONENTS, 64)
+            y[at] = n
+            add("one_bin", y)
+    for e in LIB_EXPONENTS:
+        for at in (0, 63, int(rng.integers(1, 63)), int(rng.integers(1, 63))):
+            for n in BIN_EXPONENTS + (None,):
+                y = rng.choice(BIN_EXPONENTS, 64) if n is None else np.full(64, n, dtype=np.float64)
+                y = y.astype(np.float64)
+                y[at] = e
+                add("one_lib", y)
+    for n in BIN_EXPONENTS + (None,):
+        y = (rng.choice(BIN_EXPONENTS, 64) if n is None else np.full(64, n)).astype(np.float64)
+        lib = (rng.random(64) < 1 / 3) | (lane == 0)
+        y[lib] = rng.choice(LIB_EXPONENTS, int(lib.sum()))
+        add("lib_lane0", y)
+        for first in (True, False):
+            y = np.full(64, BIN_EXPONENTS[1] if n is None else n, dtype=np.float64)
+            y[(lane < 32) == first] = rng.choice(LIB_EXPONENTS, 32)
+            add("lib_half", y)
+    for _ in range(4):
+        add("all_lib", rng.choice(LIB_EXPONENTS, 64))
+    what = np.repeat([w for w, _ in waves], 64)
+    ys = np.concatenate([y for _, y in waves])
+    # x: a third uniform, a third aimed at the lane's own exponent, the edge values sprinkled over both
+    xs = rng.random(ys.size)
+    aimed = rng.random(ys.size) < 0.5
+    xs[aimed] = 2.0 ** (-1080.0 * rng.random(int(aimed.sum())) / np.maximum(ys[aimed], 0.5))
+    edge = rng.random(ys.size) < 0.05
+    xs[edge] = rng.choice(EDGE_X[:6], int(edge.sum()))  # (x <= 1: the highlight's base is a cosine)
+    is_bin = np.isin(ys, BIN_EXPONENTS)
+    per_wave = is_bin.reshape(-1, 64).sum(axis=1)
+    assert np.all(per_wave[what.reshape(-1, 64)[:, 0] == "one_bin"] == 1)
+    assert np.all(per_wave[what.reshape(-1, 64)[:, 0] == "one_lib"] == 63)
+    assert np.all(~is_bin.reshape(-1, 64)[what.reshape(-1, 64)[:, 0] == "lib_lane0", 0])
+    assert np.all(per_wave[what.reshape(-1, 64)[:, 0] == "all_lib"] == 0)
+    want = np.empty_like(xs)
+    want[is_bin] = X.exact_pow_array(xs[is_bin], ys[is_bin].astype(np.int64))
+    big = ys == 1025
+    want[big] = X.exact_pow_array(xs[big], 1025)
+    for e, k in ((0.5, 1), (2.5, 5)):
+        m = ys == e
+        want[m] = [X.exact_pow_half(float(x), k) for x in xs[m]]
+    return xs, ys, what, is_bin, want
+
+
+def test_pow_general_mixed_waves(mixed_wave_set):
+    """RT_EVAL_POW_GENERAL on waves that mix the two kinds of exponent: the lanes on the binary
+    powering equal the correctly rounded result bit for bit (under the rule for results below
+    2**-969), in every arrangement; the lanes through pow() — 0.5 and 2.5 against the integer square
+    root of the exact power, 1025 against the exact power — are within one unit in the last place."""
+    xs, ys, what, is_bin, want = mixed_wave_set
+    got = ev(N.RT_EVAL_POW_GENERAL, xs, ys)
+    d = X.ulps_apart(got, want)
+    fails = []
+    for w in sorted(set(what.tolist())):
+        m = (what == w) & ~is_bin
+        worst = int(d[m].max()) if m.any() else 0
+        i = int(np.argmax(np.where(m, d, -1)))
+        print(f"pow mixed waves, {w}: {int(m.sum())} lanes through pow(), {int((d[m] != 0).sum())} not correctly "
+              f"rounded, largest {worst} ulp (x = {float(xs[i]).hex()}, y = {ys[i]}, got {float(got[i]).hex()}, "
+              f"want {float(want[i]).hex()})")
+        if worst > LIB_POW_ULPS:
+            fails.append(f"{w}: pow() {worst} ulp from the correctly rounded value at x = {float(xs[i]).hex()}, y = {ys[i]}")
+    assert np.all(np.isfinite(got))
+    for w in sorted(set(what.tolist())):
+        m = (what == w) & is_bin
+        if m.any():
+            report_pow(f"mixed waves, {w}, binary powering", got, want, sel=m)
+    assert not fails, "; ".join(fails)
+    # the same operands with the lanes through pow() given an exponent of the binary powering: the
+    # other lanes' bits do not depend on what their neighbours do
+    alone = ev(N.RT_EVAL_POW_GENERAL, xs, np.where(is_bin, ys, 1.0))
+    assert_bits(alone[is_bin], got[is_bin], "binary-powering lanes, with and without pow() lanes beside them",
+                (xs[is_bin], ys[is_bin]))
+
+
 # ---- 2. scenes with the exponents no other scene uses ---------------------------------------
 # Pixels not bit-identical to the oracle: the oracle's pow is glibc's.  tests/test_exact_ref.py's
 # glibc_pow_rates on 60,000 uniform x per exponent gives the fraction r of calls where it is not the
