@@ -44,7 +44,7 @@ RT_ENGINE_WAVE, RT_ENGINE_FUSED = 0, 1
 # every symbol include/rt_mi355x.h declares (tests/test_boundary.py checks the export list)
 EXPORTS = (
     "rt_abi_version", "rt_strerror", "rt_device_count", "rt_scene_check", "rt_scene_canon",
-    "rt_render", "rt_prepare", "rt_shard_rows", "rt_launch", "rt_launch_spp", "rt_launch_window", "rt_launch_samples", "rt_resolve", "rt_unshard", "rt_configure", "rt_release",
+    "rt_render", "rt_prepare", "rt_shard_rows", "rt_launch", "rt_launch_spp", "rt_launch_window", "rt_launch_samples", "rt_resolve", "rt_launch_attrs", "rt_unshard", "rt_configure", "rt_release",
     "rt_update_scene",
     "rt_ppm_bound", "rt_ppm_format", "rt_render_ppm_file",
     "rt_quantize", "rt_render_rawppm_file",
@@ -108,6 +108,13 @@ class RtStats(ctypes.Structure):
                 ("ndev", ctypes.c_int32), ("flags", ctypes.c_int32)]
 
 
+class RtAttrPlanes(ctypes.Structure):
+    """rt_attr_planes (RT_ATTRIBUTES in the header): device pointers, None = the plane is not wanted."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("precision", ctypes.c_int32), ("d_elem", ctypes.c_void_p),
+                ("d_t", ctypes.c_void_p), ("d_point", ctypes.c_void_p), ("d_normal", ctypes.c_void_p),
+                ("d_albedo", ctypes.c_void_p)]
+
+
 class RtError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
         self.code = code
@@ -152,6 +159,8 @@ def lib() -> ctypes.CDLL:
     L.rt_launch_samples.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, ctypes.c_uint64, u32, u32,
                                     vp, vp, vp]
     L.rt_resolve.argtypes = [vp, ctypes.c_uint64, u32, i32, u32, vp, vp, vp]
+    L.rt_launch_attrs.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, ctypes.c_uint64, u32,
+                                  ctypes.POINTER(RtAttrPlanes), vp]
     L.rt_ppm_bound.restype = ctypes.c_size_t
     L.rt_ppm_bound.argtypes = [u32, u32, u32]
     L.rt_ppm_format.argtypes = [vp, i32, u32, u32, u32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), vp]

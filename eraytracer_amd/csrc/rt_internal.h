@@ -110,6 +110,22 @@ struct DevGuard { // make `dev` the current device; restore the caller's on scop
 // kept; captured frame graphs are invalidated).  No launch of p may be in flight.
 int rt_prepare_scene(rt_prepared *p, const rt_elem *scene, uint32_t n);
 
+// What a unit other than rt_render.hip needs of a prepared context to launch a kernel on its scene
+// (rt_attrs.hip): the device, the header the kernels get (the filters off when RT_CFG_CULL is 0), the
+// scene tables and elem_of[compact object id] = the object's index in the caller's rt_elem array,
+// all device memory owned by p and replaced by rt_update_scene.
+namespace rtl {
+struct SceneHdr;
+}
+struct rt_scene_view {
+    int device;
+    const rtl::SceneHdr *hdr;
+    const double *tab;
+    const int *itab;
+    const int *elem_of;
+};
+rt_scene_view rt_prepared_scene(const rt_prepared *p);
+
 // Free p's wavefront work space (queues, colours, flags, lists, supersampling sums, primary
 // masks: GBs at 4096^2); the next launch grows it again.  No launch of p may be in flight.
 // Returns the bytes freed.

@@ -69,6 +69,7 @@ constexpr int TILE = 16;
 #include "rt_cull.inc"     // scene access, wave culling, candidate scans, per-lane BVH
 #include "rt_shade.inc"    // nearest-object scans, shadow tests, shading
 #include "rt_fused.inc"    // the fused engine (k_render)
+#include "rt_primary.inc"  // primary rays, the jitter, hit normals (shared with rt_attrs.hip)
 #include "rt_wave.inc"     // the wavefront engine (default)
 #include "rt_selftest.inc" // the arithmetic self-test kernels
 
@@ -117,6 +118,7 @@ struct rt_prepared {
     int cull = 1;      // rt_configure(RT_CFG_CULL)
     double *d_tab = nullptr;
     int *d_itab = nullptr;
+    int *d_elem_of = nullptr; // compact object id -> index in the caller's scene list (rt_launch_attrs)
     // wavefront-engine work space, grown on demand (one rt_launch in flight per rt_prepared):
     // grow, rt_trim and rt_release go through this one list
     enum Work {
@@ -210,23 +212,30 @@ void apply_cull(rt_prepared *p) {
 int upload_scene(rt_prepared *p, const Compiled &c) {
     DevGuard g(p->device);
     const size_t tab_bytes = c.tab.size() * sizeof(double), itab_bytes = c.itab.size() * sizeof(int);
+    const size_t elem_bytes = c.elem_of.size() * sizeof(int);
     double *tab = nullptr;
-    int *itab = nullptr;
+    int *itab = nullptr, *elem_of = nullptr;
     int rc = RT_OK;
-    if (hipMalloc(&tab, tab_bytes) != hipSuccess || hipMalloc(&itab, itab_bytes) != hipSuccess)
+    // (a scene without objects still gets a table: one int nobody reads)
+    if (hipMalloc(&tab, tab_bytes) != hipSuccess || hipMalloc(&itab, itab_bytes) != hipSuccess ||
+        hipMalloc(&elem_of, elem_bytes ? elem_bytes : sizeof(int)) != hipSuccess)
         rc = RT_ENOMEM;
     else if (hipMemcpy(tab, c.tab.data(), tab_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-             hipMemcpy(itab, c.itab.data(), itab_bytes, hipMemcpyHostToDevice) != hipSuccess)
+             hipMemcpy(itab, c.itab.data(), itab_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+             (elem_bytes && hipMemcpy(elem_of, c.elem_of.data(), elem_bytes, hipMemcpyHostToDevice) != hipSuccess))
         rc = RT_EHIP;
     if (rc != RT_OK) {
         (void)hipFree(tab); // (a null pointer is a no-op)
         (void)hipFree(itab);
+        (void)hipFree(elem_of);
         return rc;
     }
     (void)hipFree(p->d_tab);
     (void)hipFree(p->d_itab);
+    (void)hipFree(p->d_elem_of);
     p->d_tab = tab;
     p->d_itab = itab;
+    p->d_elem_of = elem_of;
     p->hdr_full = c.hdr;
     apply_cull(p);
     ++p->gen; // captured graphs hold the old tables
@@ -583,6 +592,7 @@ int rt_release(rt_prepared *p) {
     DevGuard g(p->device);
     (void)hipFree(p->d_tab);
     (void)hipFree(p->d_itab);
+    (void)hipFree(p->d_elem_of);
     free_work(p);
     for (hipEvent_t &e : p->ev_level)
         if (e) (void)hipEventDestroy(e);
@@ -601,6 +611,10 @@ int rt_release(rt_prepared *p) {
 }
 
 } // extern "C"
+
+rt_scene_view rt_prepared_scene(const rt_prepared *p) {
+    return rt_scene_view{p->device, &p->hdr, p->d_tab, p->d_itab, p->d_elem_of};
+}
 
 // Free the wavefront work space of an idle context (rt_internal.h); the next launch regrows it.
 size_t rt_trim(rt_prepared *p) {

@@ -387,6 +387,7 @@ int compile_scene(const rt_elem *in, uint32_t n, Compiled &out) {
     h.n_obj = (int)objs.size();
     h.n_light = (int)lights.size();
     h.n_org = 1 + h.n_light;
+    out.elem_of = objs; // compact ids follow list order
 
     // origins: slot 0 = camera location, slot 1+i = light i location
     std::vector<rt_vec3> org;

@@ -11,6 +11,9 @@ struct Compiled {
     SceneHdr hdr;
     std::vector<double> tab; // double table (offsets in hdr.o_*)
     std::vector<int> itab;   // int table (offsets in hdr.i_*)
+    // compact object id -> the object's index in the scene list (rt_launch_attrs' d_elem): strictly
+    // increasing, the spheres, triangles and planes of the list and nothing else
+    std::vector<int> elem_of;
 };
 
 int check_scene(const rt_elem *e, uint32_t n);

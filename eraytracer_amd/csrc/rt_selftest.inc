@@ -1,6 +1,6 @@
 // rt_selftest.inc — the arithmetic self-test kernels behind rt_selftest_math and rt_eval_math,
 // included inside rt_render.hip's anonymous namespace.
-// Expects: rt_math.inc, the wave reductions and lane_f32 of rt_cull.inc, and splitmix64 (rt_wave.inc).
+// Expects: rt_math.inc, the wave reductions and lane_f32 of rt_cull.inc, and splitmix64 (rt_primary.inc).
 
 // rt_selftest_math: sqrt_n / div_n against the device library's sqrt and division, bit for bit,
 // on operands spread log-uniformly over the ranges where the kernels use them; pow_libm's wave-

@@ -44,12 +44,7 @@ struct Rec0 {
 };
 static_assert(sizeof(Rec0) == 16, "Rec0 is one 16-byte record");
 
-// The image a raster is a window of: the raster's pixel (x, row gy) is the image's (x0 + x, y0 + gy),
-// the image IW x IH pixels.  The whole frame is {W, H, 0, 0}.  Only primary_dir's callers read it:
-// tiles, queues, masks and stores work on the raster.
-struct ImageGeom {
-    int IW, IH, x0, y0;
-};
+// (ImageGeom, splitmix64, primary_dir and hit_normal: rt_primary.inc, shared with rt_attrs.hip)
 
 // Where a pass sits in the frame (what primary_dir needs besides the pixel): the raster's width W,
 // its rows dealt to shards by raster row, and the image the raster is a window of.  The kernels that
@@ -275,13 +270,6 @@ __device__ __forceinline__ double readlane_d(double v, int l) {
     return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // A pixel's final colour for this pass.  Supersampled passes that write every pixel exactly once
 // (acc != null) fold the sample into the running sum right here, with k_accum's operations:
 // sum = acc + c (sample 0: c), kept in acc; the last sample writes sum / spp to the output
@@ -334,29 +322,6 @@ __global__ __launch_bounds__(256) void k_accum(size_t n, const double *__restric
                 reinterpret_cast<float *>(out)[i] = (float)m;
         }
     }
-}
-
-// The primary ray direction of pixel (x, image row gy) of the W x H image — image coordinates: the
-// callers add the raster's origin (ImageGeom, PassGeom) — ray_through_pixel/3 (:510-511) at
-// {X/Width, Y/Height} (:112), or the jittered sample position of RT_SUPERSAMPLING
-// (include/rt_mi355x.h).  Called by converged waves (normalize3 ballots).
-__device__ __forceinline__ D3 primary_dir(const SceneHdr &hdr, int W, int H, int spp, int sample,
-                                          unsigned long long seed, int x, int gy) {
-    double X, Y;
-    if (opq(spp) > 1) {
-        const unsigned long long pixel = (unsigned long long)gy * (unsigned)W + (unsigned)x;
-        const unsigned long long r = splitmix64(seed ^ (pixel * (unsigned)spp + (unsigned)sample));
-        // (24-bit values: one 32-bit conversion each, the same values as the 64-bit conversions)
-        const double u = (double)(unsigned)(r >> 40) * 0x1p-24, v = (double)(unsigned)((r >> 16) & 0xFFFFFFull) * 0x1p-24;
-        X = div_dim((double)x + u, W); // == / : W, H <= 2^20 (rt_launch_spp checks); x + u is exact
-        Y = div_dim((double)gy + v, H);
-    } else {
-        X = div_dim((double)x, W);
-        Y = div_dim((double)gy, H);
-    }
-    const double px = 0.0 + ((X - 0.5) * hdr.screen_w + hdr.sx);
-    const double py = (Y - 0.5) * hdr.screen_h + hdr.sy;
-    return normalize3(D3{px - hdr.cam_x, py - hdr.cam_y, hdr.dz}, hdr.prim_ok);
 }
 
 // ---- Primary rays' candidate masks, per frame geometry (k_pmask) ------------------------------
@@ -462,15 +427,6 @@ __device__ __forceinline__ HitRec rec0_to_rec(const SceneHdr &hdr, const PassGeo
 }
 __device__ __forceinline__ HitRec load_rec0(const SceneHdr &hdr, const PassGeom &g, const HitRec *q0, int slot) {
     return rec0_to_rec(hdr, g, reinterpret_cast<const Rec0 *>(q0)[slot]);
-}
-
-// Normal of object `id` at hit point h (as the reference's intersect functions compute it).
-template <int SPH = 0>
-__device__ __forceinline__ D3 hit_normal(const Scene &S, int id, const D3 &h) {
-    const double *r = obj_row<SPH>(S, id);
-    if (SPH || S.itab[S.h.i_obj_meta + id * OBJ_META_W] == K_SPHERE) // SPH: every object is a sphere
-        return normalize3(D3{h.x - r[0], h.y - r[1], h.z - r[2]}, S.h.norm_ok); // (norm_ok: spheres only)
-    return D3{r[0], r[1], r[2]};
 }
 
 // K0: q0/cnt point at level 0 of the pass; counts of levels 1..depth-1 are zeroed here too.

@@ -160,6 +160,84 @@ def render_progressive(width: int, height: int, scene=None, depth: int = 5, *, s
     return frames()
 
 
+ATTR_PLANES = ("elem", "t", "point", "normal", "albedo")  # rt_attr_planes' order
+
+
+def render_attributes(width: int, height: int, scene=None, *, planes=ATTR_PLANES, precision: str = "f64",
+                      window=None, spp: int = 1, seed: int = 0, sample: int = 0, device: int = 0):
+    """What every pixel's primary ray hits (``rt_launch_attrs``, RT_ATTRIBUTES in
+    include/rt_mi355x.h): a dict of numpy arrays, one per name in ``planes``, shaped like the frame
+    (the window's shape with ``window``): ``"elem"`` ``(h, w)`` int32, the index in ``scene`` of the
+    object hit or -1; ``"t"`` ``(h, w)``, the distance or +inf; ``"point"``, ``"normal"`` and
+    ``"albedo"`` ``(h, w, 3)``, all zero at a miss — float64 or, with ``precision="f32"``, the
+    float32 roundings of the same values.  ``spp`` > 1: the ray of sample ``sample`` of an
+    ``spp``-sample frame (RT_SUPERSAMPLING).  Bad arguments raise ValueError before the library is
+    loaded."""
+    if not _sizes_ok(width, height):
+        raise ValueError("function_clause: Width > 0, Height > 0 required (raytracer.erl:88-89)")
+    x0, y0, ww, wh = _window_ok(window, width, height)
+    if isinstance(planes, str) or not all(isinstance(n, str) for n in planes):
+        raise ValueError(f"badarg: planes must be a sequence of names from {ATTR_PLANES}, got {planes!r}")
+    names = tuple(planes)
+    if not names or len(set(names)) != len(names) or any(n not in ATTR_PLANES for n in names):
+        raise ValueError(f"badarg: planes must be distinct names from {ATTR_PLANES}, at least one, got {planes!r}")
+    if precision not in ("f64", "f32"):
+        raise ValueError(f"badarg: precision must be 'f64' or 'f32', got {precision!r}")
+    for v, n in ((spp, "spp"), (sample, "sample"), (seed, "seed"), (device, "device")):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"badarg: {n} must be an integer, got {v!r}")
+    if not 1 <= spp <= N.RT_MAX_SPP:
+        raise ValueError(f"badarg: spp must be in [1, {N.RT_MAX_SPP}], got {spp}")
+    if not 0 <= sample < spp:
+        raise ValueError(f"badarg: sample must be in [0, spp = {spp}), got {sample}")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"badarg: seed must be in [0, 2^64), got {seed}")
+    if device < 0:
+        raise ValueError(f"badarg: device must not be negative, got {device}")
+    if scene is None:
+        scene = default_scene()
+    elems = N.marshal(scene)
+    L = N.lib()
+    import torch
+    dev = torch.device("cuda", int(device))
+    fdt = torch.float64 if precision == "f64" else torch.float32
+    buf = {n: torch.empty((wh, ww) if n in ("elem", "t") else (wh, ww, 3), dtype=torch.int32 if n == "elem" else fdt,
+                          device=dev) for n in names}
+    arg = N.RtAttrPlanes(ctypes.sizeof(N.RtAttrPlanes), N.RT_OUT_F64 if precision == "f64" else N.RT_OUT_F32,
+                         *[buf[n].data_ptr() if n in buf else None for n in ATTR_PLANES])
+    p = ctypes.c_void_p()
+    N.check(L.rt_prepare(elems, len(elems), int(device), ctypes.byref(p)), "rt_prepare")
+    try:
+        # one shard of one row block per 16 rows: the slab is the window's rows
+        N.check(L.rt_launch_attrs(p, width, height, x0, y0, ww, wh, 16, 0, 1, int(spp), int(seed), int(sample),
+                                  ctypes.byref(arg), torch.cuda.current_stream(dev).cuda_stream), "rt_launch_attrs")
+        torch.cuda.synchronize(dev)
+    finally:
+        L.rt_release(p)
+    return {n: buf[n].cpu().numpy() for n in names}
+
+
+def pick(width: int, height: int, x: int, y: int, scene=None):
+    """What is under pixel (x, y) of the ``width`` x ``height`` frame: None where the primary ray
+    hits nothing, else ``{"elem": i, "term": scene[i], "t": distance, "point": (x, y, z), "normal":
+    (x, y, z), "albedo": (r, g, b)}`` — :func:`render_attributes` of the 1x1 window."""
+    if not _sizes_ok(width, height):
+        raise ValueError("function_clause: Width > 0, Height > 0 required (raytracer.erl:88-89)")
+    for v, n in ((x, "x"), (y, "y")):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"badarg: {n} must be an integer, got {v!r}")
+    if not (0 <= x < width and 0 <= y < height):
+        raise ValueError(f"badarg: pixel ({x}, {y}) is outside the {width}x{height} image")
+    if scene is None:
+        scene = default_scene()
+    a = render_attributes(width, height, scene, window=(int(x), int(y), 1, 1))
+    i = int(a["elem"][0, 0])
+    if i < 0:
+        return None
+    return {"elem": i, "term": scene[i], "t": float(a["t"][0, 0]),
+            **{n: tuple(float(v) for v in a[n][0, 0]) for n in ("point", "normal", "albedo")}}
+
+
 def _has_lights(scene) -> bool:
     from .records import tag
     return any(tag(t) == "point_light" for t in scene)

@@ -381,6 +381,53 @@ int rt_launch_samples(rt_prepared *p, uint32_t width, uint32_t height, uint32_t 
  *   d_sum or d_out or a bad out_format; n_values 0 launches nothing.  All checked before any HIP call. */
 int rt_resolve(const double *d_sum, uint64_t n_values, uint32_t samples, int out_format,
                uint32_t max_value, void *d_out, uint64_t *d_clamped, void *stream);
+/* RT_ATTRIBUTES — what a pixel's primary ray hits: the object, the distance, the point, the normal
+ * and the albedo, as planes laid out like the frame (picking, depth and normal passes, guide buffers
+ * of a denoiser).  Additive: RT_ABI_VERSION stays 5.
+ * Planes: caller-owned device memory, each laid out as rt_launch_window's slab for the same window,
+ *   row_block, shard and nshards — rt_shard_rows(win_h, row_block, nshards) rows of win_w pixels; slab
+ *   rows past the image are not written.  A null pointer is a plane not wanted and is never written.
+ *   d_elem holds one int32 per pixel, d_t one element, d_point / d_normal / d_albedo three elements;
+ *   the element of the four float planes is `precision` (RT_OUT_F64 or RT_OUT_F32), and the three
+ *   3-channel planes are RT_OUT_F64 / RT_OUT_F32 slabs in every respect: rt_unshard, rt_slab_pack and
+ *   rt_slab_unpack take them as they are.
+ * The ray of slab pixel (x, y) is the one rt_launch_window traces for sample `sample` of an spp-sample
+ *   frame: with spp = 1 (and sample = 0) the reference's ray through {X/Width, Y/Height}, with spp > 1
+ *   jittered as RT_SUPERSAMPLING defines (the window's pixels are the image's: RT_WINDOW).  There is no
+ *   depth: the attributes are the primary hit's and depend on nothing deeper.
+ * At a hit the values are what nearest_object_intersecting_ray/2 returns for that ray over the scene
+ *   list (raytracer.erl:300-346; ties keep the earlier list element, negative distances win):
+ *     d_elem    the index into the caller's rt_elem array of the object hit (>= 1: element 0 is the
+ *               camera) — the list position, not the compact id and not `canon`
+ *     d_t       Distance (it can be negative for triangles and planes)
+ *     d_point   Intersection, as the reference's intersect functions compute it (:384-390, :443-451, :471-476)
+ *     d_normal  the normal of that hit record
+ *     d_albedo  #material.colour of the object
+ *   At a miss d_elem = -1, d_t = +infinity (the reference's `infinity` start value) and the three
+ *   3-channel planes hold +0.0 in every channel, so a packed slab treats them as background.
+ *   RT_OUT_F32 stores (float) of the binary64 value; nothing is computed in binary32.
+ * Checked before any HIP call and before p is read: RT_EBADARG for a null p or planes, a struct_size
+ *   that ends before d_albedo, all five planes null, a bad precision, spp = 0, sample >= spp, a d_elem
+ *   that is not 4-byte aligned or a float plane not aligned to its element; RT_ETOOBIG for
+ *   spp > RT_MAX_SPP; the window, shard and size errors exactly as rt_launch_window.
+ * The call is asynchronous on `stream`; it neither synchronises nor allocates, and uses none of the
+ *   context's work space.  The values are bit-equal for every context configuration (culling on or
+ *   off, side streams on or off). */
+typedef struct rt_attr_planes {
+    uint32_t struct_size;   /* sizeof(rt_attr_planes) */
+    int32_t  precision;     /* RT_OUT_F64 or RT_OUT_F32: element of the four float planes */
+    int32_t *d_elem;        /* [rows][win_w]     */
+    void    *d_t;           /* [rows][win_w]     */
+    void    *d_point;       /* [rows][win_w][3]  */
+    void    *d_normal;      /* [rows][win_w][3]  */
+    void    *d_albedo;      /* [rows][win_w][3]  */
+} rt_attr_planes;
+
+int rt_launch_attrs(rt_prepared *p, uint32_t width, uint32_t height,
+                    uint32_t x0, uint32_t y0, uint32_t win_w, uint32_t win_h,
+                    uint32_t row_block, uint32_t shard, uint32_t nshards,
+                    uint32_t spp, uint64_t seed, uint32_t sample,
+                    const rt_attr_planes *planes, void *stream);
 /* Reassemble nshards gathered slabs (d_slabs = [nshards][shard_rows][W*3]) into the
  * row-major image d_image ([H][W*3]), on `stream`.  precision: the slabs' element, any of
  * RT_OUT_F64, RT_OUT_F32, RT_OUT_U8, RT_OUT_U16 (rows of W*3 elements of 8, 4, 1 or 2 bytes); the
