@@ -39,10 +39,13 @@ def sample_xy(x, y, width, height, spp=1, seed=0, sample=0):
 
 
 def scene_of(name):
-    """"default" (records.scene()), a name of scenes.named, or a name of tests/hostile.py."""
-    from tests import hostile
+    """"default" (records.scene()), a name of scenes.named, or a name of tests/hostile.py or
+    tests/hostile_flat.py."""
+    from tests import hostile, hostile_flat
     if name == "default":
         return records.scene()
+    if name in hostile_flat.NAMES:
+        return hostile_flat.build(name)
     return hostile.build(name) if name in hostile.NAMES else scenes.named(name)
 
 

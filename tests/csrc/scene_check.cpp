@@ -3,8 +3,9 @@
 // scene compiler is the library's host code that parses caller input).  Each argument is a file
 // of rt_elem records exactly as the ctypes marshal lays them out; per file it prints
 // "check canon compile n_tab n_itab" and the compiled header's flags: "cull_ok beam_ok occ_ok
-// occ_cells bvh_ok bvh_depth norm_ok prim_ok staged ext" (staged: l_bytes > 0; zeros when the scene
-// does not compile), which tests/test_hostile.py pins per hostile scene.
+// occ_cells bvh_ok bvh_depth norm_ok prim_ok staged ext n_sph n_tri n_pl n_chunk" (staged: l_bytes > 0;
+// zeros when the scene does not compile), which tests/test_hostile.py and tests/test_hostile_flat.py
+// pin per hostile scene.
 #include <cstdio>
 #include <vector>
 
@@ -25,8 +26,9 @@ int main(int argc, char **argv) {
         const int rc_compile = rc_check == RT_OK ? rtl::compile_scene(e.data(), n, c) : rc_check;
         const rtl::SceneHdr &h = c.hdr;
         std::printf("%d %d %d %zu %zu", rc_check, rc_canon, rc_compile, c.tab.size(), c.itab.size());
-        std::printf(" %d %d %d %d %d %d %d %d %d %.17g\n", h.cull_ok, h.beam_ok, h.occ_ok, h.occ_cells, h.bvh_ok,
+        std::printf(" %d %d %d %d %d %d %d %d %d %.17g", h.cull_ok, h.beam_ok, h.occ_ok, h.occ_cells, h.bvh_ok,
                     h.bvh_depth, h.norm_ok, h.prim_ok, h.l_bytes > 0 ? 1 : 0, h.ext);
+        std::printf(" %d %d %d %d\n", h.n_sph, h.n_tri, h.n_pl, h.n_chunk);
     }
     return 0;
 }

@@ -226,12 +226,14 @@ def depth(name):
 _REFS = {}
 
 
-def oracle_ref(O, name, w, h, spp=1, seed=0):
+def oracle_ref(O, name, w, h, spp=1, seed=0, scenes=None):
     """The C oracle's (frame, levels) of a hostile scene at its depth, computed once per process
-    and shared read-only among the tests."""
+    and shared read-only among the tests.  scenes: another table of name -> (builder, depth), whose
+    names are not this module's (tests/hostile_flat.py)."""
+    builder, d = (SCENES if scenes is None else scenes)[name]
     key = (name, w, h, spp, seed)
     if key not in _REFS:
-        img, lv = O.render(N.marshal(build(name)), w, h, depth(name), mode=O.MEMO, levels=True, spp=spp, seed=seed)
+        img, lv = O.render(N.marshal(builder()), w, h, d, mode=O.MEMO, levels=True, spp=spp, seed=seed)
         img.setflags(write=False)
         lv.setflags(write=False)
         _REFS[key] = (img, lv)

@@ -81,14 +81,14 @@ def test_hostile_filters_equal_brute_force(name, w, h):
 
 # ---- child processes: forced engines and environment knobs -------------------------------------
 _CHILD = r"""
-import ctypes, sys
+import ctypes, importlib, sys
 import numpy as np
 from eraytracer_amd import _native as N
 from eraytracer_amd.raytracer import render
-from tests import hostile as H
 from tests.test_gpu_frames import bench_frames, nonbitwise
 refs = np.load(sys.argv[1])
 engine, brute, names = sys.argv[2], sys.argv[3] == '1', sys.argv[4].split(',')
+H = importlib.import_module(sys.argv[5])
 L = N.lib()
 ran = 0
 for name in names:
@@ -120,26 +120,34 @@ print('hostile ok', ran, flush=True)
 """
 
 
-def _refs_file(oracle, tmp_path, names):
+def _refs_file(oracle, tmp_path, names, module=H):
     arrs = {}
     for name in names:
         for w, h in SIZES:
-            ref, rlv = H.oracle_ref(oracle, name, w, h)
+            ref, rlv = module.oracle_ref(oracle, name, w, h)
             arrs[f"{name}|{w}x{h}|rgb"], arrs[f"{name}|{w}x{h}|lv"] = ref, rlv
     path = str(tmp_path / "refs.npz")
     np.savez(path, **arrs)
     return path
 
 
-def _child(oracle, tmp_path, env, engine, brute, names):
-    path = _refs_file(oracle, tmp_path, names)
+def _child_run(oracle, tmp_path, env, engine, brute, names, module=H):
+    """The child's (count of scenes it ran, names it skipped); module: the scene table's module
+    (its build, depth and oracle_ref)."""
+    path = _refs_file(oracle, tmp_path, names, module)
     e = dict(os.environ, PYTHONPATH=ROOT, **env)
-    r = subprocess.run([sys.executable, "-c", _CHILD, path, engine, "1" if brute else "0", ",".join(names)], cwd=ROOT,
-                       env=e, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "-c", _CHILD, path, engine, "1" if brute else "0", ",".join(names),
+                        module.__name__], cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "hostile ok" in r.stdout, r.stdout[-4000:] + r.stderr[-4000:]
     ran = int(r.stdout.split("hostile ok")[1].split()[0])
     assert ran > 0
-    return ran
+    skipped = [ln.split(None, 1)[1] for ln in r.stdout.splitlines() if ln.startswith("skipped ")]
+    assert ran + len(skipped) == len(names)
+    return ran, skipped
+
+
+def _child(oracle, tmp_path, env, engine, brute, names):
+    return _child_run(oracle, tmp_path, env, engine, brute, names)[0]
 
 
 @pytest.mark.parametrize("engine", ["fused", "wave"])

@@ -97,13 +97,14 @@ def test_work_model():
 def test_scene_compiler_under_host_sanitizers(tmp_path):
     """The library's host code that parses caller input (rt_scene.cpp: check, canon, compile)
     built with AddressSanitizer + UBSan (host only; GPU sanitizers are unavailable) and run on
-    the default, S64, S256, adversarial and hostile (tests/hostile.py) scenes plus a truncated list
+    the default, S64, S256, adversarial and hostile (tests/hostile.py, tests/hostile_flat.py) scenes plus a
+    truncated list
     and a lone camera."""
     import shutil
     import subprocess
 
     from eraytracer_amd import _native as N
-    from tests import hostile
+    from tests import hostile, hostile_flat
     from tests.test_oracle import TRICKY
     if shutil.which("g++") is None:
         pytest.skip("no g++")
@@ -114,6 +115,7 @@ def test_scene_compiler_under_host_sanitizers(tmp_path):
                     os.path.join(root, "eraytracer_amd", "csrc", "rt_scene.cpp"), "-o", exe], check=True)
     scenes_ = [R.scene(), scenes.s64(), scenes.s256()] + [mk() for mk in TRICKY]
     scenes_ += [hostile.build(name) for name in hostile.NAMES]
+    scenes_ += [hostile_flat.build(name) for name in hostile_flat.NAMES]
     files = []
     for i, sc in enumerate(scenes_):
         el = N.marshal(sc)
