@@ -113,7 +113,9 @@ int rt_prepare_scene(rt_prepared *p, const rt_elem *scene, uint32_t n);
 // What a unit other than rt_render.hip needs of a prepared context to launch a kernel on its scene
 // (rt_attrs.hip): the device, the header the kernels get (the filters off when RT_CFG_CULL is 0), the
 // scene tables and elem_of[compact object id] = the object's index in the caller's rt_elem array,
-// all device memory owned by p and replaced by rt_update_scene.
+// all device memory owned by p and replaced by rt_update_scene; and (rt_query.hip) canon_of[index in
+// the caller's array] = the index of that element's canonical (first exactly equal) element, -1 for
+// an element that is not an object, n_elems entries.
 namespace rtl {
 struct SceneHdr;
 }
@@ -123,6 +125,8 @@ struct rt_scene_view {
     const double *tab;
     const int *itab;
     const int *elem_of;
+    const int *canon_of;
+    int n_elems;
 };
 rt_scene_view rt_prepared_scene(const rt_prepared *p);
 

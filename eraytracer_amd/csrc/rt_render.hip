@@ -119,6 +119,8 @@ struct rt_prepared {
     double *d_tab = nullptr;
     int *d_itab = nullptr;
     int *d_elem_of = nullptr; // compact object id -> index in the caller's scene list (rt_launch_attrs)
+    int *d_canon_of = nullptr; // scene list index -> its canonical element's index, -1: no object (rt_query_shadow)
+    int n_elems = 0;           // entries of d_canon_of: the caller's scene list
     // wavefront-engine work space, grown on demand (one rt_launch in flight per rt_prepared):
     // grow, rt_trim and rt_release go through this one list
     enum Work {
@@ -212,30 +214,36 @@ void apply_cull(rt_prepared *p) {
 int upload_scene(rt_prepared *p, const Compiled &c) {
     DevGuard g(p->device);
     const size_t tab_bytes = c.tab.size() * sizeof(double), itab_bytes = c.itab.size() * sizeof(int);
-    const size_t elem_bytes = c.elem_of.size() * sizeof(int);
+    const size_t elem_bytes = c.elem_of.size() * sizeof(int), canon_bytes = c.canon_of.size() * sizeof(int);
     double *tab = nullptr;
-    int *itab = nullptr, *elem_of = nullptr;
+    int *itab = nullptr, *elem_of = nullptr, *canon_of = nullptr;
     int rc = RT_OK;
     // (a scene without objects still gets a table: one int nobody reads)
     if (hipMalloc(&tab, tab_bytes) != hipSuccess || hipMalloc(&itab, itab_bytes) != hipSuccess ||
-        hipMalloc(&elem_of, elem_bytes ? elem_bytes : sizeof(int)) != hipSuccess)
+        hipMalloc(&elem_of, elem_bytes ? elem_bytes : sizeof(int)) != hipSuccess ||
+        hipMalloc(&canon_of, canon_bytes ? canon_bytes : sizeof(int)) != hipSuccess)
         rc = RT_ENOMEM;
     else if (hipMemcpy(tab, c.tab.data(), tab_bytes, hipMemcpyHostToDevice) != hipSuccess ||
              hipMemcpy(itab, c.itab.data(), itab_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-             (elem_bytes && hipMemcpy(elem_of, c.elem_of.data(), elem_bytes, hipMemcpyHostToDevice) != hipSuccess))
+             (elem_bytes && hipMemcpy(elem_of, c.elem_of.data(), elem_bytes, hipMemcpyHostToDevice) != hipSuccess) ||
+             (canon_bytes && hipMemcpy(canon_of, c.canon_of.data(), canon_bytes, hipMemcpyHostToDevice) != hipSuccess))
         rc = RT_EHIP;
     if (rc != RT_OK) {
         (void)hipFree(tab); // (a null pointer is a no-op)
         (void)hipFree(itab);
         (void)hipFree(elem_of);
+        (void)hipFree(canon_of);
         return rc;
     }
     (void)hipFree(p->d_tab);
     (void)hipFree(p->d_itab);
     (void)hipFree(p->d_elem_of);
+    (void)hipFree(p->d_canon_of);
     p->d_tab = tab;
     p->d_itab = itab;
     p->d_elem_of = elem_of;
+    p->d_canon_of = canon_of;
+    p->n_elems = (int)c.canon_of.size();
     p->hdr_full = c.hdr;
     apply_cull(p);
     ++p->gen; // captured graphs hold the old tables
@@ -593,6 +601,7 @@ int rt_release(rt_prepared *p) {
     (void)hipFree(p->d_tab);
     (void)hipFree(p->d_itab);
     (void)hipFree(p->d_elem_of);
+    (void)hipFree(p->d_canon_of);
     free_work(p);
     for (hipEvent_t &e : p->ev_level)
         if (e) (void)hipEventDestroy(e);
@@ -613,7 +622,7 @@ int rt_release(rt_prepared *p) {
 } // extern "C"
 
 rt_scene_view rt_prepared_scene(const rt_prepared *p) {
-    return rt_scene_view{p->device, &p->hdr, p->d_tab, p->d_itab, p->d_elem_of};
+    return rt_scene_view{p->device, &p->hdr, p->d_tab, p->d_itab, p->d_elem_of, p->d_canon_of, p->n_elems};
 }
 
 // Free the wavefront work space of an idle context (rt_internal.h); the next launch regrows it.

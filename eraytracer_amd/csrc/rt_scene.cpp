@@ -388,6 +388,8 @@ int compile_scene(const rt_elem *in, uint32_t n, Compiled &out) {
     h.n_light = (int)lights.size();
     h.n_org = 1 + h.n_light;
     out.elem_of = objs; // compact ids follow list order
+    out.canon_of.assign(n, -1);
+    for (int i : objs) out.canon_of[i] = root(e, i);
 
     // origins: slot 0 = camera location, slot 1+i = light i location
     std::vector<rt_vec3> org;

@@ -14,6 +14,9 @@ struct Compiled {
     // compact object id -> the object's index in the scene list (rt_launch_attrs' d_elem): strictly
     // increasing, the spheres, triangles and planes of the list and nothing else
     std::vector<int> elem_of;
+    // scene list index -> the index of the element's canonical (first exactly equal) element, -1 for
+    // an element that is not an object (rt_query_shadow's "same term" test): one entry per element
+    std::vector<int> canon_of;
 };
 
 int check_scene(const rt_elem *e, uint32_t n);

@@ -238,6 +238,117 @@ def pick(width: int, height: int, x: int, y: int, scene=None):
             **{n: tuple(float(v) for v in a[n][0, 0]) for n in ("point", "normal", "albedo")}}
 
 
+def _triples(a, what, n=None, shared=False):
+    """``a`` as a C-contiguous float64 ``(n, 3)`` array — or ``(3,)`` where ``shared`` allows one point
+    for the whole batch; ValueError for anything that is not an array of real numbers of that shape."""
+    try:
+        arr = np.asarray(a)
+    except Exception:
+        raise ValueError(f"badarg: {what} is not an array") from None
+    if arr.dtype == np.bool_ or not (np.issubdtype(arr.dtype, np.integer) or np.issubdtype(arr.dtype, np.floating)):
+        raise ValueError(f"badarg: {what} must hold real numbers, got dtype {arr.dtype}")
+    ok = (arr.ndim == 2 and arr.shape[1] == 3) or (shared and arr.shape == (3,))
+    if not ok:
+        raise ValueError(f"badarg: {what} must be (n, 3){' or (3,)' if shared else ''}, got {arr.shape}")
+    if arr.ndim == 2 and n is not None and arr.shape[0] != n:
+        raise ValueError(f"badarg: {what} holds {arr.shape[0]} rows, expected {n}")
+    if arr.ndim == 2 and arr.shape[0] > N.RT_MAX_QUERY_RAYS:
+        raise ValueError(f"badarg: {what} holds more than RT_MAX_QUERY_RAYS = {N.RT_MAX_QUERY_RAYS} rows")
+    return np.array(arr, dtype=np.float64, order="C")  # (a copy: the caller's array may be read-only)
+
+
+def _device_ok(device):
+    if isinstance(device, bool) or not isinstance(device, (int, np.integer)) or device < 0:
+        raise ValueError(f"badarg: device must be a non-negative integer, got {device!r}")
+
+
+def nearest_hits(origins, directions, scene=None, *, planes=ATTR_PLANES, precision: str = "f64", device: int = 0):
+    """The nearest hit of ``n`` rays of the caller's choosing (``rt_query_rays``, RT_QUERY in
+    include/rt_mi355x.h): ``directions`` is ``(n, 3)``, used as given (not normalised); ``origins`` is
+    ``(n, 3)`` or ``(3,)``, one origin for every ray.  Returns a dict of numpy arrays like
+    :func:`render_attributes`, one per name in ``planes``: ``"elem"`` ``(n,)`` int32 and ``"t"`` ``(n,)``,
+    ``"point"``, ``"normal"`` and ``"albedo"`` ``(n, 3)`` — a miss is -1, +inf and zeros.  Bad arguments
+    raise ValueError before the library is loaded."""
+    d = _triples(directions, "directions")
+    n = d.shape[0]
+    o = _triples(origins, "origins", n, shared=True)
+    if isinstance(planes, str) or not all(isinstance(p, str) for p in planes):
+        raise ValueError(f"badarg: planes must be a sequence of names from {ATTR_PLANES}, got {planes!r}")
+    names = tuple(planes)
+    if not names or len(set(names)) != len(names) or any(p not in ATTR_PLANES for p in names):
+        raise ValueError(f"badarg: planes must be distinct names from {ATTR_PLANES}, at least one, got {planes!r}")
+    if precision not in ("f64", "f32"):
+        raise ValueError(f"badarg: precision must be 'f64' or 'f32', got {precision!r}")
+    _device_ok(device)
+    if scene is None:
+        scene = default_scene()
+    elems = N.marshal(scene)
+    if n == 0:  # nothing to launch (and an empty tensor has no address to hand over)
+        fnp = np.float64 if precision == "f64" else np.float32
+        return {p: np.empty((0,) if p in ("elem", "t") else (0, 3), dtype=np.int32 if p == "elem" else fnp) for p in names}
+    L = N.lib()
+    import torch
+    dev = torch.device("cuda", int(device))
+    fdt = torch.float64 if precision == "f64" else torch.float32
+    buf = {p: torch.empty((n,) if p in ("elem", "t") else (n, 3), dtype=torch.int32 if p == "elem" else fdt, device=dev)
+           for p in names}
+    d_o, d_d = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
+    arg = N.RtAttrPlanes(ctypes.sizeof(N.RtAttrPlanes), N.RT_OUT_F64 if precision == "f64" else N.RT_OUT_F32,
+                         *[buf[p].data_ptr() if p in buf else None for p in ATTR_PLANES])
+    ctx = ctypes.c_void_p()
+    N.check(L.rt_prepare(elems, len(elems), int(device), ctypes.byref(ctx)), "rt_prepare")
+    try:
+        N.check(L.rt_query_rays(ctx, d_o.data_ptr(), d_d.data_ptr(), n, N.RT_QUERY_ONE_ORIGIN if o.ndim == 1 else 0,
+                                ctypes.byref(arg), torch.cuda.current_stream(dev).cuda_stream), "rt_query_rays")
+        torch.cuda.synchronize(dev)
+    finally:
+        L.rt_release(ctx)
+    return {p: buf[p].cpu().numpy() for p in names}
+
+
+def shadow_factors(lights, hits, elems, scene=None, *, device: int = 0):
+    """``shadow_factor/4`` for ``n`` triples (``rt_query_shadow``): ``hits`` is ``(n, 3)``, ``lights``
+    ``(n, 3)`` or ``(3,)`` (one light location for all), ``elems`` ``(n,)`` integers, the index in
+    ``scene`` of the object each hit point lies on.  Returns a ``(n,)`` uint8 array: 1 where the nearest
+    object along the ray from the light towards the hit point is that element (or a bit-identical copy
+    of it), 0 otherwise.  Bad arguments raise ValueError before the library is loaded."""
+    h = _triples(hits, "hits")
+    n = h.shape[0]
+    lt = _triples(lights, "lights", n, shared=True)
+    try:
+        e = np.asarray(elems)
+    except Exception:
+        raise ValueError("badarg: elems is not an array") from None
+    if e.dtype == np.bool_ or not np.issubdtype(e.dtype, np.integer):
+        raise ValueError(f"badarg: elems must hold integers, got dtype {e.dtype}")
+    if e.shape != (n,):
+        raise ValueError(f"badarg: elems must be ({n},), got {e.shape}")
+    if n and (e.min() < -(1 << 31) or e.max() >= 1 << 31):
+        raise ValueError("badarg: elems must fit 32-bit integers")
+    _device_ok(device)
+    if scene is None:
+        scene = default_scene()
+    marshalled = N.marshal(scene)
+    if n == 0:
+        return np.empty((0,), dtype=np.uint8)
+    L = N.lib()
+    import torch
+    dev = torch.device("cuda", int(device))
+    d_l, d_h = torch.from_numpy(lt).to(dev), torch.from_numpy(h).to(dev)
+    d_e = torch.from_numpy(np.array(e, dtype=np.int32, order="C")).to(dev)
+    lit = torch.empty((n,), dtype=torch.uint8, device=dev)
+    ctx = ctypes.c_void_p()
+    N.check(L.rt_prepare(marshalled, len(marshalled), int(device), ctypes.byref(ctx)), "rt_prepare")
+    try:
+        N.check(L.rt_query_shadow(ctx, d_l.data_ptr(), d_h.data_ptr(), d_e.data_ptr(), n,
+                                  N.RT_QUERY_ONE_ORIGIN if lt.ndim == 1 else 0, lit.data_ptr(),
+                                  torch.cuda.current_stream(dev).cuda_stream), "rt_query_shadow")
+        torch.cuda.synchronize(dev)
+    finally:
+        L.rt_release(ctx)
+    return lit.cpu().numpy()
+
+
 def _has_lights(scene) -> bool:
     from .records import tag
     return any(tag(t) == "point_light" for t in scene)

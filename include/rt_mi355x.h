@@ -428,6 +428,55 @@ int rt_launch_attrs(rt_prepared *p, uint32_t width, uint32_t height,
                     uint32_t row_block, uint32_t shard, uint32_t nshards,
                     uint32_t spp, uint64_t seed, uint32_t sample,
                     const rt_attr_planes *planes, void *stream);
+/* RT_QUERY — the same questions for rays the caller chose: the nearest hit of n arbitrary rays
+ * (rt_query_rays: nearest_object_intersecting_ray/2, raytracer.erl:300-346) and the shadow test
+ * between n pairs of points (rt_query_shadow: shadow_factor/4, :256-267), on the scene of the last
+ * rt_prepare / rt_update_scene.  Picking along a ray that is no pixel's, line of sight, "which lights
+ * see this point", a first-hit pass for a camera the reference does not have, occlusion and collision
+ * probes: each is one batch.  Additive: RT_ABI_VERSION stays 5.
+ * rt_query_rays: ray i starts at d_origin[3i..3i+2] — with RT_QUERY_ONE_ORIGIN at d_origin[0..2], one
+ *   point shared by all n rays — and has the direction d_dir[3i..3i+2].  Inputs are device memory and
+ *   always binary64.  The direction is used as given: the reference's scan does not normalise
+ *   #ray.direction, so t is in units of |direction| (and, as in the reference, a sphere's t is only a
+ *   distance for a unit direction).
+ *   out: an rt_attr_planes whose planes are flat arrays of n entries — d_elem[n], d_t[n], d_point,
+ *   d_normal and d_albedo [n][3]; `precision` (RT_OUT_F64 or RT_OUT_F32) is the element of the four
+ *   float planes; a null pointer is a plane not wanted and is never written.  Hit and miss values are
+ *   RT_ATTRIBUTES': d_elem the index in the caller's rt_elem array (ties keep the earlier list element,
+ *   negative distances of triangles and planes win), d_t the Distance, d_point origin + direction*t as
+ *   the intersect functions compute it, d_normal that hit record's normal, d_albedo #material.colour;
+ *   a miss is -1, +infinity and +0.0 in every channel.  RT_OUT_F32 stores (float) of the binary64
+ *   value; nothing is computed in binary32.
+ *   Every stored value is bit for bit what nearest_object_intersecting_ray/2 returns, for every ray
+ *   whose arithmetic stays finite in the reference (Erlang raises badarith where C gives an infinity
+ *   or a NaN).  A ray with a component that is not finite, or one whose arithmetic overflows, gets
+ *   unspecified values in its own entries; it causes no fault and has no effect on any other ray.  A
+ *   zero direction is inside the contract: it misses everything, as in the reference.
+ *   Ray i's bytes do not depend on n, on i, on the other rays of the batch, on RT_QUERY_ONE_ORIGIN
+ *   against a repeated origin, or on the context's configuration (RT_CFG_CULL, side streams).
+ *   Entries >= n of every plane are never written.
+ * rt_query_shadow: for triple i the ray from d_light[3i..] in the direction vector_normalize(d_hit[3i..]
+ *   - d_light[3i..]) (the zero vector for equal points, as vector_normalize/1 gives); d_lit[i] = 1 iff
+ *   that ray's nearest object and element d_elem[i] of the caller's rt_elem array are the same term —
+ *   equal `canon`, the renderer's rule, so another bit-identical copy of the object matches (:262) — and
+ *   0 in every other case: nothing is hit, another object is hit, or d_elem[i] is negative, >= the
+ *   scene's element count, or a camera, light or RT_OTHER element.  RT_QUERY_ONE_ORIGIN: one light
+ *   location, d_light[0..2], for all n.  Bytes >= n of d_lit are never written.
+ * Both calls are asynchronous on `stream`, neither synchronise nor allocate, and use none of the
+ *   context's work space.  n = 0 launches nothing and returns RT_OK.
+ * Checked before any HIP call and before p is read: RT_EBADARG for a null p, d_origin, d_dir, d_light,
+ *   d_hit, d_elem, d_lit or out, an unknown flag bit, an input pointer that is not 8-byte aligned
+ *   (d_elem: 4-byte), an `out` that fails rt_launch_attrs' plane checks (struct_size, all planes null,
+ *   precision, alignment); RT_ETOOBIG for n > RT_MAX_QUERY_RAYS. */
+#define RT_QUERY_ONE_ORIGIN 1   /* d_origin / d_light holds ONE point (3 doubles) shared by all n rays */
+#define RT_MAX_QUERY_RAYS (1u << 30)
+
+int rt_query_rays(rt_prepared *p, const double *d_origin, const double *d_dir, uint64_t n,
+                  uint32_t flags, const rt_attr_planes *out, void *stream);
+
+int rt_query_shadow(rt_prepared *p, const double *d_light, const double *d_hit,
+                    const int32_t *d_elem, uint64_t n, uint32_t flags,
+                    uint8_t *d_lit, void *stream);
 /* Reassemble nshards gathered slabs (d_slabs = [nshards][shard_rows][W*3]) into the
  * row-major image d_image ([H][W*3]), on `stream`.  precision: the slabs' element, any of
  * RT_OUT_F64, RT_OUT_F32, RT_OUT_U8, RT_OUT_U16 (rows of W*3 elements of 8, 4, 1 or 2 bytes); the
