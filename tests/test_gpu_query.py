@@ -23,6 +23,11 @@ beam by its rays):
                                       test_shadow_edge_cases
   k_query<0, 1, 2>                    test_shadow_queries on s256 (shadow rays are unit vectors)
   k_query<0, 1, 0>                    test_shadow_brute_force
+  the walk itself, k_query<.., 2>     tests/test_gpu_query_bvh.py: both BVH memory layouts (nodes and rows staged in
+                                      LDS, or read from HBM), trees of depth 10 to 13 and of a few nodes, whole
+                                      waves from anywhere in the walk's domain and on its limits, partial and
+                                      one-origin waves, the loop iteration after staging, rt_update_scene across
+                                      layouts (the CPU restatement of the walk: tests/test_query_bvh.py)
 """
 import ctypes
 import functools
@@ -105,7 +110,10 @@ def check(got, ref, prec, want=PLANES, what="", sel=None):
             e, g = np.ascontiguousarray(e[sel]), np.ascontiguousarray(g[sel])
         if g.tobytes() != e.tobytes():
             bad = np.flatnonzero((g.view(np.uint8).reshape(len(g), -1) != e.view(np.uint8).reshape(len(e), -1)).any(axis=1))
-            raise AssertionError(f"{what} {k} {prec}: {len(bad)} rays differ, first {bad[0]}: {g[bad[0]]!r} against {e[bad[0]]!r}")
+            at = (np.arange(len(ref[k])) if sel is None else np.arange(len(ref[k]))[sel])[bad]  # indices in the call
+            waves = sorted(set((at // 64).tolist()))  # (a wave: 64 consecutive rays of the call)
+            raise AssertionError(f"{what} {k} {prec}: {len(bad)} rays differ, first {at[0]}: {g[bad[0]]!r} against {e[bad[0]]!r}; "
+                                 f"in waves {waves}")
 
 
 def same(a, b, want=PLANES, what=""):
