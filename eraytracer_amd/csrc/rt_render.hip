@@ -51,6 +51,7 @@
 #include "../../include/rt_mi355x.h"
 #include "rt_layout.h"
 #include "rt_internal.h"
+#include "rt_plist.h"
 #include "rt_scene.h"
 
 using namespace rtl;
@@ -729,8 +730,10 @@ struct WavePlan {
     size_t slots, list0;    // record slots per level of a pass; ints before the dense lists in W_ITEMS
     size_t bytes[rt_prepared::W_COUNT]; // the work space a pass needs (0: not this plan's to grow)
     // the primary rays' candidate masks (k_pmask), of the whole slab: half-tiles, bytes (0: no masks)
-    int slab_all;
-    size_t nhalf, pmask_bytes;
+    // after the flags: the list of active tiles (pmask_list) — int rowoff[tile_rows + 1] at list_off
+    // bytes, uint2 list[tiles of the slab] at alist_off
+    int slab_all, tile_rows;
+    size_t nhalf, pmask_bytes, list_off, alist_off;
     // dynamic LDS: the SPH = 2 kernels' staged tables (0 for SPH < 2); for the reflection kernels of
     // levels that traverse the sphere BVH, after them the BVH nodes and sphere rows (when they fit
     // BVH_LDS_MAX) and every lane's stack, at the offsets rhdr carries
@@ -784,8 +787,12 @@ WavePlan wave_plan(const rt_prepared *p, const rt_frame &f, int row_begin, int r
     pl.bytes[rt_prepared::W_ITEMS] = (pl.list0 + slots * pl.nlev) * sizeof(int);
     if (hdr.beam_ok && D > 0) {
         pl.slab_all = (int)f.slab_rows();
-        pl.nhalf = (size_t)pl.tiles_x * ((pl.slab_all + TILE - 1) / TILE) * 2;
-        pl.pmask_bytes = pl.nhalf * hdr.n_chunk * 8 + pl.nhalf; // after the masks: one byte per half-tile
+        const rt_pmask_layout lay = rt_pmask_layout_of(W, pl.slab_all, hdr.n_chunk, TILE); // (rt_plist.h)
+        pl.nhalf = lay.nhalf; // (after the masks: one flag byte per half-tile)
+        pl.tile_rows = lay.tile_rows;
+        pl.list_off = lay.rowoff_off;
+        pl.alist_off = lay.list_off;
+        pl.pmask_bytes = lay.bytes;
     }
     pl.lds = pl.lds_bvh = pl.staged ? (size_t)hdr.l_bytes : 0;
     pl.rhdr = hdr;
@@ -828,13 +835,17 @@ int wave_pmask(rt_prepared *p, const WavePlan &pl, const rt_frame &f, bool super
     if (rc != RT_OK) return rc;
     const int nhalf = (int)pl.nhalf;
     const dim3 pg((unsigned)std::min<size_t>(4096, (pl.nhalf + 3) / 4));
+    const dim3 lg((unsigned)std::min(4096, (pl.tile_rows + 3) / 4)); // the list's phases 1 and 3: a wave per tile row
     unsigned long long *const masks = p->buf<unsigned long long>(rt_prepared::W_PMASK);
+    char *const base = p->buf<char>(rt_prepared::W_PMASK);
     KtScope kt(p, RT_KT_PMASK, st);
     with_bool(supersampled, [&](auto ss) {
         p->launched.note(LaunchRecord::PMASK, {decltype(ss)::value});
-        hipLaunchKernelGGL(k_pmask<decltype(ss)::value>, pg, dim3(256), 0, st, p->hdr, p->d_tab, p->d_itab, W, H, rb, sh,
-                           ns, pl.slab_all, nhalf, masks,
-                           reinterpret_cast<unsigned char *>(masks + pl.nhalf * p->hdr.n_chunk), im);
+        for (int phase = 0; phase <= 3; ++phase) // the masks and flags, then the list of active tiles (pmask_list)
+            hipLaunchKernelGGL(k_pmask<decltype(ss)::value>, phase == 0 ? pg : phase == 2 ? dim3(1) : lg, dim3(256), 0, st,
+                               p->hdr, p->d_tab, p->d_itab, W, H, rb, sh, ns, pl.slab_all, nhalf, masks,
+                               reinterpret_cast<unsigned char *>(masks + pl.nhalf * p->hdr.n_chunk), im, phase,
+                               reinterpret_cast<int *>(base + pl.list_off), reinterpret_cast<uint2 *>(base + pl.alist_off));
     });
     HIPCHK(hipGetLastError());
     std::memcpy(p->pmask_key, key, sizeof(key));
@@ -1052,6 +1063,10 @@ int wave_pass(rt_prepared *p, const WavePlan &pl, const rt_frame &f, int row0, v
     // after the masks: one byte per half-tile, 1 = every mask zero
     const unsigned short *pempty =
         pmask ? reinterpret_cast<const unsigned short *>(pmask + pl.nhalf * p->hdr.n_chunk) : nullptr;
+    // ... and the list of active tiles: the offsets from the pass's first tile row on, and the list
+    const char *const pbase = p->buf<char>(rt_prepared::W_PMASK);
+    const int *prow = pmask ? reinterpret_cast<const int *>(pbase + pl.list_off) + row0 / TILE : nullptr;
+    const uint2 *alist = pmask ? reinterpret_cast<const uint2 *>(pbase + pl.alist_off) : nullptr;
     const int sarg = sample_arg(smp.sample, smp.keep);
     ps.g = make_pass_geom(W, im, rb, sh, ns, row0, smp.spp, sarg, smp.seed, acc_p);
     const dim3 grid(std::min(ntiles, PRIMARY_GRID)); // k_primary: grid-stride loop over the tiles
@@ -1061,7 +1076,8 @@ int wave_pass(rt_prepared *p, const WavePlan &pl, const rt_frame &f, int row0, v
             p->launched.note(LaunchRecord::PRIMARY, {PREC, decltype(has_lv)::value});
             hipLaunchKernelGGL((k_primary<PREC, decltype(has_lv)::value>), grid, dim3(PRIMARY_BLOCK), 0, st, p->hdr,
                                p->d_tab, p->d_itab, W, im.y0 + H, D, rb, ps.g.yoff, ns, ps.rows, row0, ps.o, ps.lv0, ps.q,
-                               ps.counts, ntiles, smp.spp, sarg, smp.seed, acc_p, pmask, pempty, ps.nitems, ps.g.img);
+                               ps.counts, ntiles, smp.spp, sarg, smp.seed, acc_p, pmask, pempty, ps.nitems, ps.g.img,
+                               prow, alist);
         });
     }
     HIPCHK(hipGetLastError());

@@ -370,16 +370,75 @@ __device__ __forceinline__ Beam32 make_beam_corners32(const SceneHdr &h, int W, 
     return b;
 }
 
+// The active tiles of the slab — a tile is active when either of its halves has a candidate — as a
+// compact list in tile-row order, built from the empty flags by three further launches of k_pmask
+// (the flags come from many workgroups: a launch boundary makes them visible, no fence or atomic):
+//   phase 1  a wave per tile row counts the row's active tiles into rowoff[row + 1]
+//   phase 2  one workgroup turns the counts into offsets in place: rowoff[row] = active tiles in the
+//            rows before `row`, rowoff[tile_rows] = their number in the slab
+//   phase 3  a wave per tile row ballot-compacts the row's active tiles into list[rowoff[row] ...):
+//            x = tile column | half 0 empty << 30 | half 1 empty << 31, y = tile row
+// so the active tiles of any range of tile rows (a row pass) are one contiguous range of the list,
+// complete and without duplicates; k_primary's ray phase strides over it.
+constexpr unsigned PE_BOTH = 0x0101u; // a tile's two flag bytes read as one 16-bit word: both halves empty
+__device__ __forceinline__ void pmask_list(int phase, int tiles_x, int tile_rows, const unsigned short *pe2,
+                                           int *rowoff, uint2 *list) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (phase == 2) {
+        __shared__ int s_part[256];
+        const int per = (tile_rows + 255) / 256, b = min(t * per, tile_rows), e = min(b + per, tile_rows);
+        int s = 0;
+        for (int r = b; r < e; ++r) s += rowoff[r + 1];
+        s_part[t] = s;
+        __syncthreads();
+        if (t == 0) {
+            int run = 0;
+            for (int i = 0; i < 256; ++i) {
+                const int x = s_part[i];
+                s_part[i] = run;
+                run += x;
+            }
+            rowoff[0] = 0;
+        }
+        __syncthreads();
+        int run = s_part[t];
+        for (int r = b; r < e; ++r) {
+            run += rowoff[r + 1];
+            rowoff[r + 1] = run;
+        }
+        return;
+    }
+    const unsigned long long lt = (1ull << lane) - 1;
+    for (int row = blockIdx.x * 4 + wave; row < tile_rows; row += gridDim.x * 4) { // (wave-uniform)
+        int n = phase == 3 ? rowoff[row] : 0;
+        for (int c0 = 0; c0 < tiles_x; c0 += 64) {
+            const int bx = c0 + lane;
+            const unsigned f = bx < tiles_x ? (unsigned)pe2[(size_t)row * tiles_x + bx] : PE_BOTH;
+            const bool act = f != PE_BOTH;
+            const unsigned long long m = __ballot(act);
+            if (phase == 3 && act)
+                list[n + __popcll(m & lt)] = uint2{(unsigned)bx | (f & 1u) << 30 | ((f >> 8) & 1u) << 31, (unsigned)row};
+            n += __popcll(m);
+        }
+        if (phase == 1 && lane == 0) rowoff[row + 1] = n;
+    }
+}
+
 // One wave per 8x16 pixel block (k_primary's half-tiles, numbered 2 * tile + half over the whole
 // slab); masks[block * n_chunk + chunk], and pe[block] = 1 when every one of them is zero.
+// phase 0: the masks and flags; phases 1-3: the list of active tiles from the flags (pmask_list).
 template <bool JITTER>
 __global__ __launch_bounds__(256) void k_pmask(SceneHdr hdr, const double *__restrict__ tab, const int *__restrict__ itab,
                                                int W, int H, int rb, int shard, int nshards, int slab_rows, int nhalf,
-                                               unsigned long long *__restrict__ pm, unsigned char *__restrict__ pe,
-                                               ImageGeom im) {
+                                               unsigned long long *__restrict__ pm, unsigned char *pe,
+                                               ImageGeom im, int phase, int *rowoff, uint2 *list) {
     const Scene S{hdr, tab, itab};
     const int lane = threadIdx.x & 63;
     const int tiles_x = (W + TILE - 1) / TILE;
+    if (phase != 0) {
+        pmask_list(phase, tiles_x, (slab_rows + TILE - 1) / TILE, reinterpret_cast<const unsigned short *>(pe), rowoff, list);
+        return;
+    }
     for (int hw = blockIdx.x * 4 + (threadIdx.x >> 6); hw < nhalf; hw += gridDim.x * 4) { // (wave-uniform)
         const int tile = hw >> 1, half = hw & 1;
         const int by = tile / tiles_x, bx = tile - by * tiles_x;
@@ -462,7 +521,10 @@ __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restri
                                                            double *__restrict__ acc,
                                                            const unsigned long long *__restrict__ pmask,
                                                            const unsigned short *__restrict__ pempty, int *__restrict__ nitems,
-                                                           unsigned long long img) {
+                                                           unsigned long long img, const int *__restrict__ prow,
+                                                           const uint2 *__restrict__ alist) {
+    // prow, alist (with pmask, or null): k_pmask's list of active tiles, prow at the pass's first tile
+    // row — the pass's active tiles are alist[prow[0] .. prow[tile rows of the pass])
     // W: the raster's width; the image's geometry as PassGeom carries it (yoff, img; Hend = y0 + the
     // raster's height: the first image row past the raster), in two scalars more than a whole frame took.
     // this pass covers slab rows [row0, row0 + rows); out/levels point at slab row row0; pmask (or
@@ -487,22 +549,22 @@ __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restri
     const size_t pitch = (size_t)W * 3 * ESZ;
     const bool wide_ok = acc == nullptr && ((reinterpret_cast<uintptr_t>(out) | pitch) & 15) == 0;
     int it = 0;
-    // The next tile's flags are loaded a tile ahead of their use (the two halves' in one 16-bit word: one
-    // VGPR holds them across the ray work).  (A block taking two adjacent tiles in a row, so that one CU
-    // writes whole 128-byte lines of a binary32 frame, measured no better: profiles/primary_tiles_ab.txt.)
-    auto flags_of = [&](int t) { return may_skip && t < ntiles ? (unsigned)pempty[(row0 / TILE) * tiles_x + t] : 0u; };
-    unsigned flags = flags_of(blockIdx.x), flags_next;
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, flags = flags_next) {
-        flags_next = flags_of(tile + (int)gridDim.x);
-        const int by = tile / tiles_x, bx = tile - by * tiles_x;
+    const int tile0 = (row0 / TILE) * tiles_x; // the pass's first tile in the slab's numbering (masks, flags)
+    // One shard: image row = slab row + yoff, no row block to split (wave-uniform).
+    const bool single = nshards == 1;
+    // One tile of the pass (tile = by * tiles_x + bx) with its halves' empty flags, by both waves of the
+    // block.  LEAN (the two-phase pass below): the counts of levels >= 1 are zeroed wholesale and a tile
+    // with both halves empty is never filled wide here.
+    auto do_tile = [&](auto lean_c, int tile, int by, int bx, bool empty0, bool empty1) {
+        constexpr bool LEAN = decltype(lean_c)::value;
         const int x = bx * TILE + wave * 8 + (lane & 7);
         // slab row -> image row (the shard interleave, then the window's first row) without a per-lane integer division:
         // the tile's first slab row is split once (wave-uniform), the lane's offset (< 16) added
         const int ly_base = row0 + by * TILE;
-        const int q_base = ly_base / rb, r_base = ly_base - q_base * rb;
+        const int q_base = single ? 0 : ly_base / rb, r_base = ly_base - q_base * rb;
         auto image_row = [&](int lr) {
             int rr = r_base + (lr - by * TILE), qq = q_base; // slab row row0 + lr
-            while (rr >= rb) { // offset < 16: at most 16 / rb + 1 steps
+            while (!single && rr >= rb) { // offset < 16: at most 16 / rb + 1 steps
                 rr -= rb;
                 ++qq;
             }
@@ -514,16 +576,13 @@ __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restri
         const int lr0 = by * TILE + (lane >> 3), lr1 = lr0 + 8;
         // (the wave's entry at a wave-uniform address; both waves read both halves' flags)
         const int wv = __builtin_amdgcn_readfirstlane(wave); // (a scalar: what it selects stays wave-uniform)
-        const unsigned long long *pm =
-            pmask ? pmask + ((size_t)((row0 / TILE) * tiles_x + tile) * 2 + wv) * hdr.n_chunk : nullptr;
-        const unsigned fl = __builtin_amdgcn_readfirstlane(flags);
-        const bool empty0 = (fl & 0xffu) != 0, empty1 = (fl >> 8) != 0;
+        const unsigned long long *pm = pmask ? pmask + ((size_t)(tile0 + tile) * 2 + wv) * hdr.n_chunk : nullptr;
         const bool mine_empty = wv ? empty1 : empty0, other_empty = wv ? empty0 : empty1;
         RT_STAT(ST_WAVES, 1);
         RT_STAT(ST_PRIM_WAVES, 1);
         if (mine_empty) {
             RT_STAT(ST_PRIM_EMPTY, 1);
-            const bool fill = other_empty && wide_ok;
+            const bool fill = (!LEAN || LEVELS) && other_empty && wide_ok;
             if (fill) {
                 RT_STAT(ST_PRIM_FILL, 1);
                 // the tile's columns inside the image: a multiple of 16 bytes per row, as the pitch is
@@ -554,9 +613,14 @@ __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restri
             }
             // (an empty wave has no count to give, and needs the other's only for the tile's total:
             // the live wave of such a tile writes the counts)
-            if (other_empty)
-                for (int l = tid; l < depth; l += PRIMARY_BLOCK) cnt[(size_t)l * ntiles + tile] = 0;
-            continue;
+            if (other_empty) {
+                if (LEAN) {
+                    if (tid == 0) cnt[tile] = 0;
+                } else {
+                    for (int l = tid; l < depth; l += PRIMARY_BLOCK) cnt[(size_t)l * ntiles + tile] = 0;
+                }
+            }
+            return;
         }
         auto pixel = [&](int lr, bool &inside, bool &active, D3 &d) {
             const int iy = image_row(lr);
@@ -608,9 +672,99 @@ __global__ RT_PRIMARY_BOUNDS void k_primary(SceneHdr hdr, const double *__restri
         const int base = tile * TILE_SLOTS + before;
         emit(h0, in0, d0, id0, t0, lr0, base + __popcll(m0 & lt));
         emit(h1, in1, d1, id1, t1, lr1, base + __popcll(m0) + __popcll(m1 & lt));
-        // (the tile's counts: by both waves' lanes, or by the live wave's alone)
-        for (int l = other_empty ? lane : tid; l < depth; l += other_empty ? 64 : PRIMARY_BLOCK)
-            cnt[(size_t)l * ntiles + tile] = l == 0 ? total : 0;
+        // (the tile's counts: by both waves' lanes, or by the live wave's alone; LEAN: level 0's only)
+        if (LEAN) {
+            if ((other_empty ? lane : tid) == 0) cnt[tile] = total;
+        } else {
+            for (int l = other_empty ? lane : tid; l < depth; l += other_empty ? 64 : PRIMARY_BLOCK)
+                cnt[(size_t)l * ntiles + tile] = l == 0 ? total : 0;
+        }
+    };
+    // Sphere-only scenes with masks, one sample per pixel: the pass in two phases that share nothing but
+    // the kernel's arguments.  (Masks exist only at depth >= 1.)
+    if (may_skip && spp == 1 && prow != nullptr) {
+        const int gtid = blockIdx.x * PRIMARY_BLOCK + tid, gthreads = gridDim.x * PRIMARY_BLOCK;
+        // The tile counts k_items and the appends start from: levels >= 1 are zeroed here, coalesced and
+        // spread over the grid; level 0 of a tile has one writer, the phase that owns the tile, so no
+        // zero races an active tile's total.
+        if (depth > 1) {
+            int *const z = cnt + ntiles;
+            const size_t n = (size_t)(depth - 1) * ntiles;
+            const size_t head = min(n, (size_t)((0 - (reinterpret_cast<uintptr_t>(z) >> 2)) & 3)); // ints up to 16 bytes
+            const size_t nv = (n - head) >> 2;
+            for (size_t i = gtid; i < nv; i += gthreads) reinterpret_cast<int4 *>(z + head)[i] = int4{0, 0, 0, 0};
+            if ((size_t)gtid < head) z[gtid] = 0;
+            if (head + nv * 4 + gtid < n) z[head + nv * 4 + gtid] = 0; // (fewer than 4 left)
+        }
+        const int trows = (rows + TILE - 1) / TILE; // tile rows of the pass
+        // Background phase: the tiles with both halves empty are written black.
+        if (!LEVELS && wide_ok) {
+            // Streamed: a wave takes 64 consecutive 16-byte vectors of a tile row's raster rows and writes
+            // those inside empty tiles down the tile row's rows, so runs of adjacent empty tiles are
+            // written as whole lines; the lane of a tile's first vector zeroes the tile's level-0 count.
+            // The units (tile row, chunk of 64 vectors) advance by adding: nothing is divided per unit.
+            constexpr int VPT = TILE * 3 * ESZ / 16; // vectors per tile and row: 12 (f32) or 24 (f64)
+            const int vrow = (int)(pitch >> 4), chunks = (vrow + 63) >> 6;
+            const int wv = __builtin_amdgcn_readfirstlane(wave);
+            const int ustep = (int)gridDim.x * (PRIMARY_BLOCK / 64), dq = ustep / chunks, dr = ustep - dq * chunks;
+            const int u0 = (int)blockIdx.x * (PRIMARY_BLOCK / 64) + wv;
+            int by = u0 / chunks, c = u0 - by * chunks;
+            while (by < trows) {
+                // the tile row's rows inside the pass and the image (image rows grow with slab rows)
+                int nr;
+                if (single) {
+                    nr = min(TILE, min(rows, Hend - yoff - row0) - by * TILE);
+                } else {
+                    for (nr = 0; nr < TILE; ++nr) {
+                        const int lr = by * TILE + nr, sr = row0 + lr, qq = sr / rb;
+                        if (!(lr < rows && qq * nshards * rb + (sr - qq * rb) + yoff < Hend)) break;
+                    }
+                }
+                const int v = c * 64 + lane_id();
+                const int bx = v / VPT;
+                const unsigned f = v < vrow ? (unsigned)pempty[tile0 + by * tiles_x + bx] : 0u;
+                if (f == PE_BOTH) {
+                    char *ptr = static_cast<char *>(out) + (size_t)by * TILE * pitch + (size_t)v * 16;
+                    for (int r = 0; r < nr; ++r, ptr += pitch) *reinterpret_cast<uint4 *>(ptr) = uint4{0u, 0u, 0u, 0u};
+                    if (v == bx * VPT) cnt[by * tiles_x + bx] = 0;
+                }
+                by += dq;
+                c += dr;
+                if (c >= chunks) {
+                    c -= chunks;
+                    ++by;
+                }
+            }
+        } else {
+            // Narrow (unaligned rasters, running sums, levels): the empty tiles one by one.
+            for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+                const unsigned f = __builtin_amdgcn_readfirstlane((unsigned)pempty[tile0 + tile]);
+                if (f != PE_BOTH) continue;
+                const int by = tile / tiles_x;
+                do_tile(std::true_type{}, tile, by, tile - by * tiles_x, true, true);
+            }
+        }
+        // Ray phase: the active tiles, from k_pmask's list.
+        const int a0 = prow[0], nact = prow[trows] - a0;
+        for (int i = blockIdx.x; i < nact; i += gridDim.x) {
+            const uint2 e = alist[a0 + i];
+            const int ex = __builtin_amdgcn_readfirstlane((int)e.x), ey = __builtin_amdgcn_readfirstlane((int)e.y);
+            const int bx = ex & 0x3fffffff, by = ey - row0 / TILE;
+            do_tile(std::true_type{}, by * tiles_x + bx, by, bx, ((unsigned)ex >> 30 & 1u) != 0, (unsigned)ex >> 31 != 0);
+        }
+        return;
+    }
+    // Everything else (brute force, mixed and beam-free scenes, supersampled passes): every tile in turn.
+    // The next tile's flags are loaded a tile ahead of their use (the two halves' in one 16-bit word: one
+    // VGPR holds them across the ray work).  (A block taking two adjacent tiles in a row, so that one CU
+    // writes whole 128-byte lines of a binary32 frame, measured no better: profiles/primary_tiles_ab.txt.)
+    auto flags_of = [&](int t) { return may_skip && t < ntiles ? (unsigned)pempty[tile0 + t] : 0u; };
+    unsigned flags = flags_of(blockIdx.x), flags_next;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, flags = flags_next) {
+        flags_next = flags_of(tile + (int)gridDim.x);
+        const int by = tile / tiles_x;
+        const unsigned fl = __builtin_amdgcn_readfirstlane(flags);
+        do_tile(std::false_type{}, tile, by, tile - by * tiles_x, (fl & 0xffu) != 0, (fl >> 8) != 0);
     }
 }
 
