@@ -6,8 +6,9 @@
 // traces the ray rt_launch_window traces (primary_dir, rt_primary.inc) through the same nearest
 // scan (nearest_pair, the wave building its own binary32 beam: no cached masks, no queues, none of
 // the wavefront engine's work space), and derives the hit's geometry with the primitives the
-// shading kernels use (Camera + Direction*t, hit_normal, the OBJ_W row), so every value is the one
-// the renderer itself would shade.  Everything is binary64; RT_OUT_F32 rounds at the store.
+// shading kernels use (Camera + Direction*t, hit_normal, the OBJ_W row: hit_attrs, rt_planes.inc,
+// shared with rt_query.hip like the stores), so every value is the one the renderer itself would
+// shade.  Everything is binary64; RT_OUT_F32 rounds at the store.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -20,6 +21,7 @@
 #include "../../include/rt_mi355x.h"
 #include "rt_layout.h"
 #include "rt_internal.h"
+#include "rt_pick.h"
 
 using namespace rtl;
 
@@ -31,35 +33,12 @@ constexpr int TILE = 16;
 #include "rt_cull.inc"    // scene access, wave culling, candidate scans
 #include "rt_shade.inc"   // nearest-object scans
 #include "rt_primary.inc" // primary rays, the jitter, hit normals
+#include "rt_planes.inc"  // the attribute planes: a hit's attributes, the stores
 
 constexpr int ATTR_BLOCK = 128; // two waves: the halves of a 16x16 tile
 constexpr int ATTR_GRID = 8192; // blocks at most (k_primary's grid)
 // Tiles per launch: a slab with more (a column of 2^20 rows, 2^16 tiles wide) takes several.
 constexpr int ATTR_MAX_TILES = 1 << 30;
-
-// The caller's planes as the kernel takes them; a null pointer is a plane not wanted.
-struct AttrPlanes {
-    int *elem;
-    void *t, *point, *normal, *albedo;
-};
-
-template <int PREC>
-__device__ __forceinline__ void put1(void *plane, size_t pix, double v) {
-    if (PREC == RT_OUT_F64)
-        reinterpret_cast<double *>(plane)[pix] = v;
-    else
-        reinterpret_cast<float *>(plane)[pix] = (float)v;
-}
-template <int PREC>
-__device__ __forceinline__ void put3(void *plane, size_t pix, const D3 &c) {
-    if (PREC == RT_OUT_F64) {
-        double *o = reinterpret_cast<double *>(plane) + pix * 3;
-        o[0] = c.x; o[1] = c.y; o[2] = c.z;
-    } else {
-        float *o = reinterpret_cast<float *>(plane) + pix * 3;
-        o[0] = (float)c.x; o[1] = (float)c.y; o[2] = (float)c.z;
-    }
-}
 
 // Slab rows [row0, row0 + ntiles / tiles_x * 16) of the raster (W pixels wide, slab_rows rows; its
 // rows dealt to shards as k_primary's: rb, yoff = y0 + shard * rb, nshards; Hend = y0 + the raster's
@@ -72,7 +51,7 @@ __global__ __launch_bounds__(ATTR_BLOCK) void k_attrs(SceneHdr hdr, const double
                                                      const int *__restrict__ itab, const int *__restrict__ elem_of,
                                                      int W, int Hend, int rb, int yoff, int nshards, int slab_rows,
                                                      int row0, int ntiles, int spp, int sample, unsigned long long seed,
-                                                     ImageGeom im, AttrPlanes pl) {
+                                                     ImageGeom im, HitPlanes pl) {
     const Scene S{hdr, tab, itab};
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const D3 cam = {hdr.cam_x, hdr.cam_y, hdr.cam_z};
@@ -105,28 +84,8 @@ __global__ __launch_bounds__(ATTR_BLOCK) void k_attrs(SceneHdr hdr, const double
         nearest_pair<FAST>(S, 0, cam, d0, d1, in0, in1, id0, t0, id1, t1, nullptr);
         const bool any_hit = __ballot(id0 >= 0 || id1 >= 0) != 0; // (then the scene has an object: row 0 exists)
         auto emit = [&](bool inside, const D3 &d, int id, double t, int off) {
-            const bool hit = id >= 0;
-            const int row = hit ? id : 0; // a lane without a hit goes through the geometry of object 0, unstored
-            D3 h = {0.0, 0.0, 0.0}, n = h, a = h;
-            int e = -1;
-            if (any_hit) { // (wave-uniform)
-                if (want_geom) {
-                    // Intersection = Camera + Direction*t (:384-387 and its kin), the normal of that hit record
-                    h = D3{cam.x + d.x * t, cam.y + d.y * t, cam.z + d.z * t};
-                    n = hit_normal<0>(S, row, h);
-                }
-                const double *m = obj_row<0>(S, row);
-                a = D3{m[3], m[4], m[5]}; // #material.colour
-                e = elem_of[row];
-            }
-            if (!inside) return;
-            const size_t pix = (size_t)(sr_base + off) * W + x;
-            const D3 zero = {0.0, 0.0, 0.0};
-            if (pl.elem) pl.elem[pix] = hit ? e : -1;
-            if (pl.t) put1<PREC>(pl.t, pix, hit ? t : __builtin_inf());
-            if (pl.point) put3<PREC>(pl.point, pix, hit ? h : zero);
-            if (pl.normal) put3<PREC>(pl.normal, pix, hit ? n : zero);
-            if (pl.albedo) put3<PREC>(pl.albedo, pix, hit ? a : zero);
+            const HitAttrs a = hit_attrs(S, elem_of, cam, d, id, t, any_hit, want_geom);
+            if (inside) put_hit<PREC>(pl, (size_t)(sr_base + off) * W + x, id, t, a);
         };
         emit(in0, d0, id0, t0, off0);
         emit(in1, d1, id1, t1, off1);
@@ -139,17 +98,14 @@ extern "C" int rt_launch_attrs(rt_prepared *p, uint32_t width, uint32_t height, 
                                uint32_t win_h, uint32_t row_block, uint32_t shard, uint32_t nshards, uint32_t spp,
                                uint64_t seed, uint32_t sample, const rt_attr_planes *planes, void *stream) {
     if (!p || !planes) return RT_EBADARG;
-    if (planes->struct_size < offsetof(rt_attr_planes, d_albedo) + sizeof(planes->d_albedo)) return RT_EBADARG;
-    const rt_attr_planes pl = *planes;
-    if (!pl.d_elem && !pl.d_t && !pl.d_point && !pl.d_normal && !pl.d_albedo) return RT_EBADARG;
-    if (pl.precision != RT_OUT_F64 && pl.precision != RT_OUT_F32) return RT_EBADARG;
+    HitPlanes hp;
+    int prec;
+    const int planes_ok = rt_hit_planes(planes, &hp, &prec);
+    if (prec < 0) return planes_ok;
     if (spp == 0) return RT_EBADARG;
-    if (spp > RT_MAX_SPP) return RT_ETOOBIG;
+    if (spp > RT_MAX_SPP) return RT_ETOOBIG; // (reported before a misaligned plane)
     if (sample >= spp) return RT_EBADARG;
-    const uintptr_t esz = pl.precision == RT_OUT_F64 ? 8 : 4;
-    if ((uintptr_t)pl.d_elem % 4) return RT_EBADARG;
-    for (const void *f : {pl.d_t, pl.d_point, pl.d_normal, pl.d_albedo})
-        if ((uintptr_t)f % esz) return RT_EBADARG;
+    if (planes_ok != RT_OK) return planes_ok;
     rt_frame f = {};
     f.img_w = width;
     f.img_h = height;
@@ -158,7 +114,7 @@ extern "C" int rt_launch_attrs(rt_prepared *p, uint32_t width, uint32_t height, 
     f.row_block = row_block;
     f.shard = shard;
     f.nshards = nshards;
-    f.precision = pl.precision;
+    f.precision = prec;
     f.order = RT_ORDER_EXACT;
     f.spp = spp;
     f.seed = seed;
@@ -173,24 +129,18 @@ extern "C" int rt_launch_attrs(rt_prepared *p, uint32_t width, uint32_t height, 
     // rows per launch: whole tile rows, ATTR_MAX_TILES tiles at most
     const int pass_rows = (int)std::min<long long>(slab_rows, (long long)std::max(1, ATTR_MAX_TILES / tiles_x) * TILE);
     const ImageGeom im = {(int)width, (int)height, (int)x0, (int)y0};
-    const AttrPlanes ap = {pl.d_elem, pl.d_t, pl.d_point, pl.d_normal, pl.d_albedo};
     for (int row0 = 0; row0 < slab_rows; row0 += pass_rows) {
         const int rows = std::min(pass_rows, slab_rows - row0);
         const int ntiles = tiles_x * ((rows + TILE - 1) / TILE);
         const dim3 grid(std::min(ntiles, ATTR_GRID));
-        auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(ATTR_BLOCK), 0, st, *v.hdr, v.tab, v.itab, v.elem_of, W,
-                               (int)(y0 + win_h), rb, (int)(y0 + shard * row_block), (int)nshards, slab_rows, row0, ntiles,
-                               (int)spp, (int)sample, (unsigned long long)seed, im, ap);
-        };
-        const bool fast = v.hdr->cull_ok != 0;
-        if (pl.precision == RT_OUT_F64) {
-            if (fast) launch(k_attrs<RT_OUT_F64, true>);
-            else launch(k_attrs<RT_OUT_F64, false>);
-        } else {
-            if (fast) launch(k_attrs<RT_OUT_F32, true>);
-            else launch(k_attrs<RT_OUT_F32, false>);
-        }
+        with_int<RT_OUT_F64, RT_OUT_F32>(prec, [&](auto pc) {
+            with_bool(v.hdr->cull_ok != 0, [&](auto fast) {
+                hipLaunchKernelGGL((k_attrs<decltype(pc)::value, decltype(fast)::value>), grid, dim3(ATTR_BLOCK), 0, st,
+                                   *v.hdr, v.tab, v.itab, v.elem_of, W, (int)(y0 + win_h), rb,
+                                   (int)(y0 + shard * row_block), (int)nshards, slab_rows, row0, ntiles, (int)spp,
+                                   (int)sample, (unsigned long long)seed, im, hp);
+            });
+        });
         if (hipGetLastError() != hipSuccess) return RT_EHIP;
     }
     return RT_OK;

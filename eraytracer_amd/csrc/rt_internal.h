@@ -7,6 +7,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <initializer_list>
+
 #include "../../include/rt_mi355x.h"
 #include "rt_shard.h"
 
@@ -129,6 +131,30 @@ struct rt_scene_view {
     int n_elems;
 };
 rt_scene_view rt_prepared_scene(const rt_prepared *p);
+
+// The caller's hit-attribute planes as the kernels take them (rt_planes.inc); a null pointer is a
+// plane not wanted.
+struct HitPlanes {
+    int *elem;
+    void *t, *point, *normal, *albedo;
+};
+// The plane checks of rt_launch_attrs and rt_query_rays, in this order: the struct's size, at least
+// one plane, the precision — *precision is -1 until these have passed — and every plane aligned to
+// its element.  RT_OK (and *out filled) or RT_EBADARG.  Calls nothing.
+inline int rt_hit_planes(const rt_attr_planes *planes, HitPlanes *out, int *precision) {
+    *precision = -1;
+    if (planes->struct_size < offsetof(rt_attr_planes, d_albedo) + sizeof(planes->d_albedo)) return RT_EBADARG;
+    const rt_attr_planes pl = *planes;
+    if (!pl.d_elem && !pl.d_t && !pl.d_point && !pl.d_normal && !pl.d_albedo) return RT_EBADARG;
+    if (pl.precision != RT_OUT_F64 && pl.precision != RT_OUT_F32) return RT_EBADARG;
+    *precision = pl.precision;
+    const uintptr_t esz = pl.precision == RT_OUT_F64 ? 8 : 4;
+    if ((uintptr_t)pl.d_elem % 4) return RT_EBADARG;
+    for (const void *f : {pl.d_t, pl.d_point, pl.d_normal, pl.d_albedo})
+        if ((uintptr_t)f % esz) return RT_EBADARG;
+    *out = HitPlanes{pl.d_elem, pl.d_t, pl.d_point, pl.d_normal, pl.d_albedo};
+    return RT_OK;
+}
 
 // Free p's wavefront work space (queues, colours, flags, lists, supersampling sums, primary
 // masks: GBs at 4096^2); the next launch grows it again.  No launch of p may be in flight.

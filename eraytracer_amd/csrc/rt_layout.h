@@ -15,6 +15,7 @@
 // per-object origin terms (sphere o-c and C, triangle T and Q, plane V0) are tabled per
 // origin.  Origin slot 0 = camera, slot 1+i = point light i.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace rtl {
@@ -123,5 +124,20 @@ struct SceneHdr {
     double n_light_d; // number of lights as a double (ORDER_FAST weight)
     double ext;       // largest |coordinate| (+ radius) of the origins and spheres (binary32 culling margins)
 };
+
+// The dynamic LDS of a launch whose lanes walk the sphere BVH (stage_bvh and scan_bvh, rt_cull.inc),
+// from byte `base` (a multiple of 16: the staged rows are copied 16 bytes at a time) for workgroups
+// of `block` threads: the nodes and the sphere rows when they fit BVH_LDS_MAX (l_bvh, l_bsph; both
+// -1 otherwise: read from HBM), then at l_stack every lane's stack — block * bvh_depth words, which
+// is what scan_bvh indexes by wave and lane.  Returns the launch's dynamic LDS in bytes, base included.
+inline size_t bvh_lds_place(SceneHdr &h, size_t base, int block) {
+    const size_t nb = (size_t)h.n_bvh * BVH_NODE_DOUBLES * 8, sb = (size_t)h.n_sph * SPH_W * 8;
+    const bool fits = nb + sb <= (size_t)BVH_LDS_MAX;
+    h.l_bvh = fits ? (int)base : -1;
+    h.l_bsph = fits ? (int)(base + nb) : -1;
+    if (fits) base += nb + sb;
+    h.l_stack = (int)base;
+    return base + (size_t)block * h.bvh_depth * sizeof(unsigned);
+}
 
 } // namespace rtl

@@ -9,7 +9,8 @@
 // gets) — and all of it in binary64; RT_OUT_F32 rounds at the store.  The scans, sqrt_x and
 // normalize3 reduce across the wave, so a wave stays converged from its loads to the end of the
 // geometry: a lane past the batch traces a copy of the last ray with act = false, and only the stores
-// are predicated.
+// are predicated.  What a hit means and how the planes are stored is rt_attrs.hip's (hit_attrs and
+// put_hit, rt_planes.inc).
 //
 // SCAN — how a wave finds the nearest object; every form computes the reference's binary64 tests on
 // the objects it keeps and the (t, list position) minimum, so all give the same bits:
@@ -62,6 +63,7 @@
 #include "../../include/rt_mi355x.h"
 #include "rt_layout.h"
 #include "rt_internal.h"
+#include "rt_pick.h"
 
 using namespace rtl;
 
@@ -71,35 +73,12 @@ namespace {
 #include "rt_cull.inc"    // scene access, wave culling, candidate scans, the per-lane BVH
 #include "rt_shade.inc"   // nearest-object scans
 #include "rt_primary.inc" // hit normals
+#include "rt_planes.inc"  // the attribute planes: a hit's attributes, the stores
 
 constexpr int QUERY_BLOCK = 256; // four waves
 constexpr int QUERY_GRID = 8192; // blocks at most: a batch above 2^21 rays loops
 enum { MODE_RAYS = 0, MODE_SHADOW = 1 };
 enum { SCAN_BRUTE = 0, SCAN_BEAM = 1, SCAN_BVH = 2 };
-
-// The caller's planes as the kernel takes them; a null pointer is a plane not wanted.
-struct QueryPlanes {
-    int *elem;
-    void *t, *point, *normal, *albedo;
-};
-
-template <int PREC>
-__device__ __forceinline__ void put1(void *plane, size_t i, double v) {
-    if (PREC == RT_OUT_F64)
-        reinterpret_cast<double *>(plane)[i] = v;
-    else
-        reinterpret_cast<float *>(plane)[i] = (float)v;
-}
-template <int PREC>
-__device__ __forceinline__ void put3(void *plane, size_t i, const D3 &c) {
-    if (PREC == RT_OUT_F64) {
-        double *o = reinterpret_cast<double *>(plane) + i * 3;
-        o[0] = c.x; o[1] = c.y; o[2] = c.z;
-    } else {
-        float *o = reinterpret_cast<float *>(plane) + i * 3;
-        o[0] = (float)c.x; o[1] = (float)c.y; o[2] = (float)c.z;
-    }
-}
 
 // The BVH's domain (see the top of this file); E = hdr.ext + 1.
 __device__ __forceinline__ bool bvh_domain(const D3 &o, const D3 &d, double E) {
@@ -118,7 +97,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_query(SceneHdr hdr, const doubl
                                                       const int *__restrict__ canon_of, int n_elems,
                                                       const double *__restrict__ a, const double *__restrict__ b,
                                                       const int *__restrict__ elem, unsigned long long n, int one_origin,
-                                                      QueryPlanes pl, uint8_t *__restrict__ lit) {
+                                                      HitPlanes pl, uint8_t *__restrict__ lit) {
     const Scene S{hdr, tab, itab};
     if (SCAN == SCAN_BVH) stage_bvh(S); // (every thread of the block: it ends in a barrier)
     const int lane = threadIdx.x & 63;
@@ -143,85 +122,48 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_query(SceneHdr hdr, const doubl
             const bool walk = SCAN == SCAN_BVH && __ballot(act && !bvh_domain(o, d, hdr.ext + 1.0)) == 0;
             id = nearest<false, false, 0, false>(S, 0, o, d, t, act, 0, walk);
         }
-        const bool hit = id >= 0;
-        const bool any_hit = __ballot(hit) != 0; // (then the scene has an object: row 0 exists)
-        const int row = hit ? id : 0; // a lane without a hit goes through the geometry of object 0, unstored
+        const bool any_hit = __ballot(id >= 0) != 0; // (then the scene has an object: row 0 exists)
         if (MODE == MODE_SHADOW) {
             // lit iff the nearest object and element e are the same term: the same canonical element
             int same = 0;
-            if (any_hit) { // (wave-uniform)
+            if (any_hit) { // (wave-uniform; a lane without a hit reads object 0's row, unstored)
                 const int e = elem[j];
                 const int ce = (e >= 0 && e < n_elems) ? canon_of[e] : -1; // -1: not an object of the scene
-                const int ch = elem_of[obj_meta<0>(S, row).z];
-                same = hit && ce >= 0 && ce == ch;
+                const int ch = elem_of[obj_meta<0>(S, id >= 0 ? id : 0).z];
+                same = id >= 0 && ce >= 0 && ce == ch;
             }
             if (act) lit[i] = (uint8_t)same;
             continue;
         }
-        D3 h = {0.0, 0.0, 0.0}, nrm = h, alb = h;
-        int e = -1;
-        if (any_hit) { // (wave-uniform)
-            if (want_geom) {
-                // Intersection = Origin + Direction*t (:384-387 and its kin), the normal of that hit record
-                h = D3{o.x + d.x * t, o.y + d.y * t, o.z + d.z * t};
-                nrm = hit_normal<0>(S, row, h);
-            }
-            const double *m = obj_row<0>(S, row);
-            alb = D3{m[3], m[4], m[5]}; // #material.colour
-            e = elem_of[row];
-        }
-        if (!act) continue;
-        const D3 zero = {0.0, 0.0, 0.0};
-        if (pl.elem) pl.elem[i] = hit ? e : -1;
-        if (pl.t) put1<PREC>(pl.t, i, hit ? t : __builtin_inf());
-        if (pl.point) put3<PREC>(pl.point, i, hit ? h : zero);
-        if (pl.normal) put3<PREC>(pl.normal, i, hit ? nrm : zero);
-        if (pl.albedo) put3<PREC>(pl.albedo, i, hit ? alb : zero);
+        const HitAttrs at = hit_attrs(S, elem_of, o, d, id, t, any_hit, want_geom);
+        if (act) put_hit<PREC>(pl, i, id, t, at);
     }
 }
 
 // One launch of n > 0 queries on p's scene; the arguments are checked.
 template <int MODE>
 int rt_query_launch(rt_prepared *p, int prec, const double *a, const double *b, const int *elem, uint64_t n,
-                    uint32_t flags, const QueryPlanes &pl, uint8_t *lit, void *stream) {
+                    uint32_t flags, const HitPlanes &pl, uint8_t *lit, void *stream) {
     const rt_scene_view v = rt_prepared_scene(p);
     DevGuard g(v.device);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     // The kernel's header: a copy with the host-proven shortcuts off (they were proved for the
-    // renderer's rays) and, for a scene with a BVH, this launch's dynamic LDS laid out as the
-    // reflection kernels' (rt_render.hip, wave_plan) with this kernel's block size: the nodes and the
-    // sphere rows when they fit BVH_LDS_MAX, then every lane's stack.
+    // renderer's rays) and, for a scene with a BVH, this launch's dynamic LDS placed in it.
     SceneHdr h = *v.hdr;
     h.norm_ok = h.prim_ok = 0;
     h.l_bvh = h.l_bsph = -1;
     h.l_stack = 0;
     const int scan = !h.cull_ok ? SCAN_BRUTE : h.bvh_ok ? SCAN_BVH : SCAN_BEAM;
-    size_t lds = 0;
-    if (scan == SCAN_BVH) {
-        const size_t nb = (size_t)h.n_bvh * BVH_NODE_DOUBLES * 8, sb = (size_t)h.n_sph * SPH_W * 8;
-        if (nb + sb <= (size_t)BVH_LDS_MAX) {
-            h.l_bvh = 0;
-            h.l_bsph = (int)nb;
-            lds = nb + sb;
-        }
-        h.l_stack = (int)lds;
-        lds += (size_t)QUERY_BLOCK * h.bvh_depth * sizeof(unsigned);
-    }
+    const size_t lds = scan == SCAN_BVH ? bvh_lds_place(h, 0, QUERY_BLOCK) : 0;
     const dim3 grid((unsigned)std::min<uint64_t>((n + QUERY_BLOCK - 1) / QUERY_BLOCK, QUERY_GRID));
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(QUERY_BLOCK), lds, st, h, v.tab, v.itab, v.elem_of, v.canon_of, v.n_elems, a,
-                           b, elem, (unsigned long long)n, (int)(flags & RT_QUERY_ONE_ORIGIN), pl, lit);
-    };
-    auto by_scan = [&](auto brute, auto beam, auto bvh) {
-        if (scan == SCAN_BRUTE) launch(brute);
-        else if (scan == SCAN_BEAM) launch(beam);
-        else launch(bvh);
-    };
     // (the shadow answers have no float plane: one PREC)
-    if (MODE == MODE_SHADOW || prec == RT_OUT_F64)
-        by_scan(k_query<RT_OUT_F64, MODE, SCAN_BRUTE>, k_query<RT_OUT_F64, MODE, SCAN_BEAM>, k_query<RT_OUT_F64, MODE, SCAN_BVH>);
-    else if constexpr (MODE == MODE_RAYS)
-        by_scan(k_query<RT_OUT_F32, MODE, SCAN_BRUTE>, k_query<RT_OUT_F32, MODE, SCAN_BEAM>, k_query<RT_OUT_F32, MODE, SCAN_BVH>);
+    with_int<RT_OUT_F64, MODE == MODE_SHADOW ? RT_OUT_F64 : RT_OUT_F32>(prec, [&](auto pc) {
+        with_int<SCAN_BRUTE, SCAN_BVH>(scan, [&](auto sc) {
+            hipLaunchKernelGGL((k_query<decltype(pc)::value, MODE, decltype(sc)::value>), grid, dim3(QUERY_BLOCK), lds, st,
+                               h, v.tab, v.itab, v.elem_of, v.canon_of, v.n_elems, a, b, elem, (unsigned long long)n,
+                               (int)(flags & RT_QUERY_ONE_ORIGIN), pl, lit);
+        });
+    });
     return hipGetLastError() == hipSuccess ? RT_OK : RT_EHIP;
 }
 
@@ -232,19 +174,12 @@ extern "C" int rt_query_rays(rt_prepared *p, const double *d_origin, const doubl
     if (!p || !d_origin || !d_dir || !out) return RT_EBADARG;
     if (flags & ~(uint32_t)RT_QUERY_ONE_ORIGIN) return RT_EBADARG;
     if ((uintptr_t)d_origin % 8 || (uintptr_t)d_dir % 8) return RT_EBADARG;
-    // rt_launch_attrs' plane checks
-    if (out->struct_size < offsetof(rt_attr_planes, d_albedo) + sizeof(out->d_albedo)) return RT_EBADARG;
-    const rt_attr_planes pl = *out;
-    if (!pl.d_elem && !pl.d_t && !pl.d_point && !pl.d_normal && !pl.d_albedo) return RT_EBADARG;
-    if (pl.precision != RT_OUT_F64 && pl.precision != RT_OUT_F32) return RT_EBADARG;
-    const uintptr_t esz = pl.precision == RT_OUT_F64 ? 8 : 4;
-    if ((uintptr_t)pl.d_elem % 4) return RT_EBADARG;
-    for (const void *f : {pl.d_t, pl.d_point, pl.d_normal, pl.d_albedo})
-        if ((uintptr_t)f % esz) return RT_EBADARG;
+    HitPlanes hp;
+    int prec;
+    if (rt_hit_planes(out, &hp, &prec) != RT_OK) return RT_EBADARG;
     if (n > RT_MAX_QUERY_RAYS) return RT_ETOOBIG;
     if (n == 0) return RT_OK;
-    const QueryPlanes qp = {pl.d_elem, pl.d_t, pl.d_point, pl.d_normal, pl.d_albedo};
-    return rt_query_launch<MODE_RAYS>(p, pl.precision, d_origin, d_dir, nullptr, n, flags, qp, nullptr, stream);
+    return rt_query_launch<MODE_RAYS>(p, prec, d_origin, d_dir, nullptr, n, flags, hp, nullptr, stream);
 }
 
 extern "C" int rt_query_shadow(rt_prepared *p, const double *d_light, const double *d_hit, const int32_t *d_elem, uint64_t n,
@@ -254,6 +189,6 @@ extern "C" int rt_query_shadow(rt_prepared *p, const double *d_light, const doub
     if ((uintptr_t)d_light % 8 || (uintptr_t)d_hit % 8 || (uintptr_t)d_elem % 4) return RT_EBADARG;
     if (n > RT_MAX_QUERY_RAYS) return RT_ETOOBIG;
     if (n == 0) return RT_OK;
-    const QueryPlanes none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const HitPlanes none = {nullptr, nullptr, nullptr, nullptr, nullptr};
     return rt_query_launch<MODE_SHADOW>(p, RT_OUT_F64, d_light, d_hit, d_elem, n, flags, none, d_lit, stream);
 }

@@ -51,6 +51,7 @@
 #include "../../include/rt_mi355x.h"
 #include "rt_layout.h"
 #include "rt_internal.h"
+#include "rt_pick.h"
 #include "rt_plist.h"
 #include "rt_scene.h"
 
@@ -317,28 +318,7 @@ struct KtScope {
     }
 };
 
-// ---- picking a kernel template: a run-time value handed to a generic lambda as a compile-time
-// constant (a std::integral_constant argument c; decltype(c)::value is the template argument).
-// Every helper returns what the lambda returns.
-template <typename F>
-auto with_bool(bool v, F &&f) {
-    return v ? f(std::true_type{}) : f(std::false_type{});
-}
-// v in [LO, HI] (a value above HI is taken as HI)
-template <int LO, int HI, typename F>
-auto with_int(int v, F &&f) {
-    if constexpr (LO < HI) {
-        if (v != LO) return with_int<LO + 1, HI>(v, f);
-    }
-    return f(std::integral_constant<int, LO>{});
-}
-// f(PREC, GENPOW): the output precision (RT_OUT_F64 / RT_OUT_F32) and whether the scene needs the general pow
-template <typename F>
-auto with_prec_pow(int precision, bool int_pow, F &&f) {
-    return with_int<RT_OUT_F64, RT_OUT_F32>(precision, [&](auto prec) {
-        return with_bool(!int_pow, [&](auto genpow) { return f(prec, genpow); });
-    });
-}
+// ---- picking a kernel template (with_bool, with_int, with_prec_pow: rt_pick.h)
 // f(SPH): 2 = spheres only with the tables staged in LDS, 1 = spheres only, 0 = any scene
 template <typename F>
 auto with_sph(bool staged, bool sph_only, F &&f) {
@@ -796,16 +776,7 @@ WavePlan wave_plan(const rt_prepared *p, const rt_frame &f, int row_begin, int r
     }
     pl.lds = pl.lds_bvh = pl.staged ? (size_t)hdr.l_bytes : 0;
     pl.rhdr = hdr;
-    if (pl.rhdr.bvh_ok) {
-        const size_t nb = (size_t)hdr.n_bvh * BVH_NODE_DOUBLES * 8, sb = (size_t)hdr.n_sph * SPH_W * 8;
-        if (nb + sb <= (size_t)BVH_LDS_MAX) {
-            pl.rhdr.l_bvh = (int)pl.lds_bvh;
-            pl.rhdr.l_bsph = (int)(pl.lds_bvh + nb);
-            pl.lds_bvh += nb + sb;
-        }
-        pl.rhdr.l_stack = (int)pl.lds_bvh;
-        pl.lds_bvh += (size_t)BLOCK * hdr.bvh_depth * sizeof(unsigned);
-    }
+    if (pl.rhdr.bvh_ok) pl.lds_bvh = bvh_lds_place(pl.rhdr, pl.lds, BLOCK);
     return pl;
 }
 

@@ -22,6 +22,7 @@ malformed scene is a ``badarg`` (ValueError) instead of a crash in a worker proc
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import time
 
@@ -163,6 +164,41 @@ def render_progressive(width: int, height: int, scene=None, depth: int = 5, *, s
 ATTR_PLANES = ("elem", "t", "point", "normal", "albedo")  # rt_attr_planes' order
 
 
+def _planes_ok(planes, precision):
+    """The tuple of plane names; ValueError for names or a precision rt_attr_planes does not have."""
+    if isinstance(planes, str) or not all(isinstance(n, str) for n in planes):
+        raise ValueError(f"badarg: planes must be a sequence of names from {ATTR_PLANES}, got {planes!r}")
+    names = tuple(planes)
+    if not names or len(set(names)) != len(names) or any(n not in ATTR_PLANES for n in names):
+        raise ValueError(f"badarg: planes must be distinct names from {ATTR_PLANES}, at least one, got {planes!r}")
+    if precision not in ("f64", "f32"):
+        raise ValueError(f"badarg: precision must be 'f64' or 'f32', got {precision!r}")
+    return names
+
+
+def _plane_buffers(names, precision, lead, dev):
+    """A tensor on ``dev`` per name — ``lead`` or ``lead + (3,)`` — and the RtAttrPlanes pointing at them."""
+    import torch
+    fdt = torch.float64 if precision == "f64" else torch.float32
+    buf = {n: torch.empty(lead if n in ("elem", "t") else lead + (3,), dtype=torch.int32 if n == "elem" else fdt,
+                          device=dev) for n in names}
+    return buf, N.RtAttrPlanes(ctypes.sizeof(N.RtAttrPlanes), N.RT_OUT_F64 if precision == "f64" else N.RT_OUT_F32,
+                               *[buf[n].data_ptr() if n in buf else None for n in ATTR_PLANES])
+
+
+@contextlib.contextmanager
+def _prepared(L, elems, dev):
+    """The scene ``elems`` prepared on ``dev``: (handle, current stream); synchronised, then released, on exit."""
+    import torch
+    p = ctypes.c_void_p()
+    N.check(L.rt_prepare(elems, len(elems), dev.index, ctypes.byref(p)), "rt_prepare")
+    try:
+        yield p, torch.cuda.current_stream(dev).cuda_stream
+        torch.cuda.synchronize(dev)
+    finally:
+        L.rt_release(p)
+
+
 def render_attributes(width: int, height: int, scene=None, *, planes=ATTR_PLANES, precision: str = "f64",
                       window=None, spp: int = 1, seed: int = 0, sample: int = 0, device: int = 0):
     """What every pixel's primary ray hits (``rt_launch_attrs``, RT_ATTRIBUTES in
@@ -176,13 +212,7 @@ def render_attributes(width: int, height: int, scene=None, *, planes=ATTR_PLANES
     if not _sizes_ok(width, height):
         raise ValueError("function_clause: Width > 0, Height > 0 required (raytracer.erl:88-89)")
     x0, y0, ww, wh = _window_ok(window, width, height)
-    if isinstance(planes, str) or not all(isinstance(n, str) for n in planes):
-        raise ValueError(f"badarg: planes must be a sequence of names from {ATTR_PLANES}, got {planes!r}")
-    names = tuple(planes)
-    if not names or len(set(names)) != len(names) or any(n not in ATTR_PLANES for n in names):
-        raise ValueError(f"badarg: planes must be distinct names from {ATTR_PLANES}, at least one, got {planes!r}")
-    if precision not in ("f64", "f32"):
-        raise ValueError(f"badarg: precision must be 'f64' or 'f32', got {precision!r}")
+    names = _planes_ok(planes, precision)
     for v, n in ((spp, "spp"), (sample, "sample"), (seed, "seed"), (device, "device")):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
             raise ValueError(f"badarg: {n} must be an integer, got {v!r}")
@@ -200,20 +230,11 @@ def render_attributes(width: int, height: int, scene=None, *, planes=ATTR_PLANES
     L = N.lib()
     import torch
     dev = torch.device("cuda", int(device))
-    fdt = torch.float64 if precision == "f64" else torch.float32
-    buf = {n: torch.empty((wh, ww) if n in ("elem", "t") else (wh, ww, 3), dtype=torch.int32 if n == "elem" else fdt,
-                          device=dev) for n in names}
-    arg = N.RtAttrPlanes(ctypes.sizeof(N.RtAttrPlanes), N.RT_OUT_F64 if precision == "f64" else N.RT_OUT_F32,
-                         *[buf[n].data_ptr() if n in buf else None for n in ATTR_PLANES])
-    p = ctypes.c_void_p()
-    N.check(L.rt_prepare(elems, len(elems), int(device), ctypes.byref(p)), "rt_prepare")
-    try:
+    buf, arg = _plane_buffers(names, precision, (wh, ww), dev)
+    with _prepared(L, elems, dev) as (p, stream):
         # one shard of one row block per 16 rows: the slab is the window's rows
         N.check(L.rt_launch_attrs(p, width, height, x0, y0, ww, wh, 16, 0, 1, int(spp), int(seed), int(sample),
-                                  ctypes.byref(arg), torch.cuda.current_stream(dev).cuda_stream), "rt_launch_attrs")
-        torch.cuda.synchronize(dev)
-    finally:
-        L.rt_release(p)
+                                  ctypes.byref(arg), stream), "rt_launch_attrs")
     return {n: buf[n].cpu().numpy() for n in names}
 
 
@@ -272,13 +293,7 @@ def nearest_hits(origins, directions, scene=None, *, planes=ATTR_PLANES, precisi
     d = _triples(directions, "directions")
     n = d.shape[0]
     o = _triples(origins, "origins", n, shared=True)
-    if isinstance(planes, str) or not all(isinstance(p, str) for p in planes):
-        raise ValueError(f"badarg: planes must be a sequence of names from {ATTR_PLANES}, got {planes!r}")
-    names = tuple(planes)
-    if not names or len(set(names)) != len(names) or any(p not in ATTR_PLANES for p in names):
-        raise ValueError(f"badarg: planes must be distinct names from {ATTR_PLANES}, at least one, got {planes!r}")
-    if precision not in ("f64", "f32"):
-        raise ValueError(f"badarg: precision must be 'f64' or 'f32', got {precision!r}")
+    names = _planes_ok(planes, precision)
     _device_ok(device)
     if scene is None:
         scene = default_scene()
@@ -289,20 +304,11 @@ def nearest_hits(origins, directions, scene=None, *, planes=ATTR_PLANES, precisi
     L = N.lib()
     import torch
     dev = torch.device("cuda", int(device))
-    fdt = torch.float64 if precision == "f64" else torch.float32
-    buf = {p: torch.empty((n,) if p in ("elem", "t") else (n, 3), dtype=torch.int32 if p == "elem" else fdt, device=dev)
-           for p in names}
+    buf, arg = _plane_buffers(names, precision, (n,), dev)
     d_o, d_d = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
-    arg = N.RtAttrPlanes(ctypes.sizeof(N.RtAttrPlanes), N.RT_OUT_F64 if precision == "f64" else N.RT_OUT_F32,
-                         *[buf[p].data_ptr() if p in buf else None for p in ATTR_PLANES])
-    ctx = ctypes.c_void_p()
-    N.check(L.rt_prepare(elems, len(elems), int(device), ctypes.byref(ctx)), "rt_prepare")
-    try:
+    with _prepared(L, elems, dev) as (ctx, stream):
         N.check(L.rt_query_rays(ctx, d_o.data_ptr(), d_d.data_ptr(), n, N.RT_QUERY_ONE_ORIGIN if o.ndim == 1 else 0,
-                                ctypes.byref(arg), torch.cuda.current_stream(dev).cuda_stream), "rt_query_rays")
-        torch.cuda.synchronize(dev)
-    finally:
-        L.rt_release(ctx)
+                                ctypes.byref(arg), stream), "rt_query_rays")
     return {p: buf[p].cpu().numpy() for p in names}
 
 
@@ -337,15 +343,9 @@ def shadow_factors(lights, hits, elems, scene=None, *, device: int = 0):
     d_l, d_h = torch.from_numpy(lt).to(dev), torch.from_numpy(h).to(dev)
     d_e = torch.from_numpy(np.array(e, dtype=np.int32, order="C")).to(dev)
     lit = torch.empty((n,), dtype=torch.uint8, device=dev)
-    ctx = ctypes.c_void_p()
-    N.check(L.rt_prepare(marshalled, len(marshalled), int(device), ctypes.byref(ctx)), "rt_prepare")
-    try:
+    with _prepared(L, marshalled, dev) as (ctx, stream):
         N.check(L.rt_query_shadow(ctx, d_l.data_ptr(), d_h.data_ptr(), d_e.data_ptr(), n,
-                                  N.RT_QUERY_ONE_ORIGIN if lt.ndim == 1 else 0, lit.data_ptr(),
-                                  torch.cuda.current_stream(dev).cuda_stream), "rt_query_shadow")
-        torch.cuda.synchronize(dev)
-    finally:
-        L.rt_release(ctx)
+                                  N.RT_QUERY_ONE_ORIGIN if lt.ndim == 1 else 0, lit.data_ptr(), stream), "rt_query_shadow")
     return lit.cpu().numpy()
 
 
