@@ -28,13 +28,13 @@
 #include <vector>
 
 #include "../../include/rt_mi355x.h"
+#include "rt_bands.h"
 #include "rt_internal.h"
 #include "rt_scene.h"
 
 namespace {
 
 constexpr int RT_CTX_PER_DEVICE = 4;
-constexpr int MAX_BANDS = 64;
 // target output bytes per band (RT_BAND_MB overrides, for A/B runs)
 size_t band_bytes() {
     static const size_t b = [] {
@@ -79,8 +79,8 @@ struct rt_ctx {
     bool busy = false;
     hipStream_t render = nullptr, copy = nullptr, copy2 = nullptr; // copy2: a second DMA queue for pinned frames
     hipEvent_t e0 = nullptr, e1 = nullptr;      // timing: around the render launches
-    hipEvent_t band[MAX_BANDS] = {};             // band i rendered
-    hipEvent_t copied[MAX_BANDS] = {};           // band i copied to the host (staging or pinned)
+    hipEvent_t band[MAX_BANDS] = {};             // band rt_bands::event(i, b) rendered
+    hipEvent_t copied[MAX_BANDS] = {};           // ... and copied to the host (staging or pinned)
     rt_prepared *p = nullptr;
     std::vector<unsigned char> key;              // bytes of the scene p was prepared from
     void *d_buf[3] = {};
@@ -174,16 +174,6 @@ bool is_pinned(const void *p, size_t bytes) {
         return a.type == hipMemoryTypeHost;
     };
     return bytes > 0 && one(p) && one(static_cast<const char *>(p) + bytes - 1);
-}
-
-uint32_t lcm_u(uint32_t a, uint32_t b) {
-    uint32_t x = a, y = b;
-    while (y) {
-        const uint32_t t = x % y;
-        x = y;
-        y = t;
-    }
-    return a / x * b;
 }
 
 } // namespace
@@ -466,184 +456,205 @@ int rt_reset_contexts(void) {
     return busy;
 }
 
-int rt_render(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, uint32_t depth, const rt_opts *opts,
-              void *out_rgb, rt_stats *stats) {
-    uint32_t width = img_w, height = img_h; // the window's from the window checks on
-    auto t_begin = std::chrono::steady_clock::now();
-    if (width == 0 && height == 0) return RT_DONE;
-    if (width == 0 || height == 0) return RT_EBADARG;
+} // extern "C"
+
+// ---- rt_render, in stages ---------------------------------------------------------------------
+namespace {
+
+struct RenderDev { // a used device: its context and its buffers, for all of the device's shards
+    rt_ctx *c = nullptr;
+    char *d_ren = nullptr, *d_out = nullptr; // the slabs the kernels render into, the slabs the copies read
+    char *stage = nullptr;
+    uint8_t *d_lv = nullptr;
+    uint64_t *d_cl = nullptr;
+};
+// What the stages share: the call, its plan and its devices.
+struct Render {
+    const rt_elem *scene;
+    uint32_t n, img_w, img_h, depth;
+    char *out;     // the caller's frame
+    rt_opts o;     // the options, loaded; ndev resolved
+    rt_window win; // the raster this call renders and returns
+    bool integer, pinned;
+    rt_bands plan;
+    // an integer frame is rendered in binary64 (frame.precision, rrow bytes per row) and quantised band
+    // by band into the integer slab; rowbytes / slab_bytes describe what is copied to the host
+    uint32_t rowbytes;
+    size_t rrow, rslab_bytes, slab_bytes;
+    rt_frame frame; // what every shard renders (its index filled in per shard): the window, in the render precision
+    std::vector<RenderDev> dev;
+    rt_shard_map map(uint32_t shard) const { return rt_shard_map{win.h, o.row_block, shard, plan.nshards}; }
+};
+
+// The argument checks in their documented order, then the plan.  No HIP call before the device count.
+int render_plan(Render &r, const rt_opts *opts, void *out_rgb) {
+    if (r.img_w == 0 && r.img_h == 0) return RT_DONE;
+    if (r.img_w == 0 || r.img_h == 0) return RT_EBADARG;
     if (!out_rgb) return RT_EBADARG;
-    rt_opts o;
+    rt_opts &o = r.o;
     rt_opts_load(opts, &o);
-    const bool integer = o.precision == RT_OUT_U8 || o.precision == RT_OUT_U16;
-    if (o.precision != RT_OUT_F64 && o.precision != RT_OUT_F32 && !integer) return RT_EBADARG;
-    if (integer && o.max_value > (o.precision == RT_OUT_U8 ? 255u : (uint32_t)RT_MAX_INT_VALUE)) return RT_ETOOBIG;
+    if (!rt_format_ok(o.precision)) return RT_EBADARG;
+    r.integer = rt_is_int(o.precision);
+    if (r.integer && o.max_value > rt_max_value_of(o.precision)) return RT_ETOOBIG;
     if (o.order != RT_ORDER_EXACT && o.order != RT_ORDER_FAST) return RT_EBADARG;
     if (o.spp > RT_MAX_SPP) return RT_ETOOBIG;
-    if (width > (1u << 20) || height > (1u << 20)) return RT_ETOOBIG;
-    // The window (opts->win_*): from here on (width, height) is the raster this call renders and
-    // returns — slabs, bands, staging, levels and the scatter are sized on it — and only
-    // rt_launch_rows is handed the image's (img_w, img_h) and the origin.
-    rt_window win;
-    int rc = rt_opts_window(o, img_w, img_h, &win);
+    if (r.img_w > (1u << 20) || r.img_h > (1u << 20)) return RT_ETOOBIG;
+    // The window (opts->win_*): from here on win is the raster this call renders and returns —
+    // slabs, bands, staging, levels and the scatter are sized on it — and only rt_launch_rows is
+    // handed the image's (img_w, img_h) and the origin.
+    int rc = rt_opts_window(o, r.img_w, r.img_h, &r.win);
     if (rc != RT_OK) return rc;
-    width = win.w;
-    height = win.h;
-    rc = rtl::check_scene(scene, n);
+    rc = rtl::check_scene(r.scene, r.n);
     if (rc != RT_OK) return rc;
     int navail = 0;
     if (hipGetDeviceCount(&navail) != hipSuccess || navail <= 0) return RT_ENODEV;
-    const int alias = device_alias();
-    if (alias > 0) {
+    if (device_alias() > 0) {
         if (o.first_dev < 0 || o.first_dev >= navail) return RT_ENODEV;
-        navail = o.first_dev + alias;
+        navail = o.first_dev + device_alias();
     }
     if (o.ndev < 0) o.ndev = navail - o.first_dev;
     if (o.first_dev < 0 || o.ndev <= 0 || o.first_dev + o.ndev > navail) return RT_ENODEV;
-    const uint32_t ns = o.nshards ? o.nshards : (uint32_t)o.ndev, rb = o.row_block;
+    const uint32_t ns = o.nshards ? o.nshards : (uint32_t)o.ndev;
     if (ns > RT_MAX_SHARDS) return RT_ETOOBIG;
     const uint32_t nd = std::min<uint32_t>(ns, (uint32_t)o.ndev); // devices used; shard s on device s % nd
-    const uint32_t slab = rt_shard_rows(height, rb, ns);
-    // an integer frame is rendered in binary64 (render_prec, rrow bytes per row) and quantised band
-    // by band into the integer slab; esz / rowbytes / slab_bytes describe what is copied to the host
-    const int render_prec = integer ? RT_OUT_F64 : o.precision;
-    const size_t esz = o.precision == RT_OUT_U8 ? 1 : o.precision == RT_OUT_U16 ? 2 : o.precision == RT_OUT_F32 ? 4 : 8;
-    const uint32_t rowbytes = width * 3 * (uint32_t)esz;
-    const size_t rrow = (size_t)width * 3 * (render_prec == RT_OUT_F32 ? 4 : 8), rslab_bytes = (size_t)slab * rrow;
-    const size_t frame_bytes = (size_t)height * rowbytes, slab_bytes = (size_t)slab * rowbytes;
-    const bool pinned = is_pinned(out_rgb, frame_bytes);
-    // bands: whole row blocks and whole tiles, about band_bytes() of output each, at most
-    // MAX_BANDS per device over all of its shards
-    const uint32_t per_dev = (ns + nd - 1) / nd;
-    const uint32_t max_nb = std::max<uint32_t>(1, MAX_BANDS / per_dev);
-    const uint32_t gran = lcm_u(rb, 16);
-    uint32_t band = (uint32_t)std::max<size_t>(1, band_bytes() / rowbytes) / gran * gran;
-    band = std::max(band, gran);
-    if ((slab + band - 1) / band > max_nb) band = ((slab + max_nb - 1) / max_nb + gran - 1) / gran * gran;
-    const uint32_t nb = (slab + band - 1) / band;
+    r.frame = rt_opts_frame(o, r.img_w, r.img_h, r.win, r.depth);
+    r.frame.nshards = ns;
+    r.frame.precision = r.integer ? RT_OUT_F64 : o.precision;
+    r.rowbytes = r.win.w * 3 * (uint32_t)rt_elem_size(o.precision);
+    r.plan = rt_band_plan(r.win.h, o.row_block, ns, nd, r.rowbytes, band_bytes());
+    r.rrow = (size_t)r.win.w * 3 * rt_elem_size(r.frame.precision);
+    r.rslab_bytes = (size_t)r.plan.slab * r.rrow;
+    r.slab_bytes = (size_t)r.plan.slab * r.rowbytes;
+    r.out = static_cast<char *>(out_rgb);
+    r.pinned = is_pinned(out_rgb, (size_t)r.win.h * r.rowbytes);
+    r.dev.assign(nd, RenderDev());
+    return RT_OK;
+}
 
-    DevGuard restore; // (the loops below select each context's device themselves)
-    std::vector<rt_ctx *> ctx(nd, nullptr);
-    std::vector<char *> d_out(nd, nullptr), stage(nd, nullptr); // d_out: the slabs the copies read
-    std::vector<char *> d_ren(nd, nullptr);                     // the slabs the kernels render into
-    std::vector<uint8_t *> d_lv(nd, nullptr);
-    std::vector<uint64_t *> d_cl(nd, nullptr);
-    // what every shard renders (its index filled in per shard): the window, in render_prec
-    rt_frame frame = rt_opts_frame(o, img_w, img_h, win, depth);
-    frame.nshards = ns;
-    frame.precision = render_prec;
+// an allocation that fails while other contexts of the device sit idle on their memory is
+// retried once after those are trimmed (trim_idle)
+template <typename F>
+int retry_trimmed(int dev, F &&alloc) {
+    int e = alloc();
+    if (e == RT_ENOMEM && trim_idle(dev) > 0) e = alloc();
+    return e;
+}
+
+// Device d's context, made current, and its buffers.
+int render_acquire(Render &r, uint32_t d) {
+    RenderDev &v = r.dev[d];
+    const int dev = device_alias() > 0 ? r.o.first_dev : r.o.first_dev + (int)d;
+    int err = rt_ctx_acquire(dev, r.scene, r.n, &v.c);
+    if (err != RT_OK) return err;
+    (void)hipSetDevice(dev);
+    const uint32_t k = r.plan.shards_of(d);
+    auto buffer = [&](int which, size_t bytes, void *out) {
+        return retry_trimmed(dev, [&] { return rt_ctx_device_buffer(v.c, which, bytes, static_cast<void **>(out)); });
+    };
+    err = buffer(0, k * r.rslab_bytes, &v.d_ren);
+    v.d_out = v.d_ren;
+    if (err == RT_OK && r.integer) {
+        err = buffer(2, k * r.slab_bytes, &v.d_out);
+        if (err == RT_OK) err = rt_ctx_clamped(v.c, &v.d_cl);
+        if (err == RT_OK && hipMemsetAsync(v.d_cl, 0, sizeof(uint64_t), v.c->render) != hipSuccess) err = RT_EHIP;
+    }
+    if (err == RT_OK && r.o.out_levels) err = buffer(1, (size_t)k * r.plan.slab * r.win.w, &v.d_lv);
+    if (err == RT_OK && !r.pinned)
+        err = rt_ctx_host_buffer(v.c, 2 * (size_t)r.plan.band * r.rowbytes, reinterpret_cast<void **>(&v.stage));
+    return err;
+}
+
+// Band b of device d's i-th shard (r.frame.shard): its render on the render stream and, into a
+// pinned frame, its copy on a copy stream behind it.
+int render_band(Render &r, uint32_t d, uint32_t i, uint32_t b) {
+    const RenderDev &v = r.dev[d];
+    rt_ctx *c = v.c;
+    const uint32_t slab = r.plan.slab, ev = r.plan.event(i, b);
+    char *slab_out = v.d_out + i * r.slab_bytes, *slab_ren = v.d_ren + i * r.rslab_bytes;
+    uint8_t *slab_lv = r.o.out_levels ? v.d_lv + (size_t)i * slab * r.win.w : nullptr;
+    const uint32_t b0 = r.plan.row0(b), b1 = r.plan.row1(b);
+    // image rows of the shard = its slab rows [0, valid): the rest of the slab is never rendered
+    const uint32_t end = std::min(b1, r.frame.valid_rows());
+    int err = retry_trimmed(c->device, [&] { // (a failed grow launches nothing)
+        return rt_launch_rows(c->p, r.frame, b0, b1, slab_ren, slab_lv, c->render, (r.o.flags & RT_LEVELS_HIT) ? 1 : 0);
+    });
+    // integer frame: the band's image rows quantised behind its render, before its event
+    if (err == RT_OK && r.integer && b0 < end)
+        err = rt_quantize(slab_ren + (size_t)b0 * r.rrow, RT_OUT_F64, (uint64_t)(end - b0) * r.win.w * 3, r.o.max_value,
+                          r.o.precision, slab_out + (size_t)b0 * r.rowbytes, v.d_cl, c->render);
+    if (err == RT_OK && hipEventRecord(c->band[ev], c->render) != hipSuccess) err = RT_EHIP;
+    if (err == RT_OK && r.pinned) {
+        hipStream_t cs = (ev % copy_streams()) ? c->copy2 : c->copy;
+        if (hipStreamWaitEvent(cs, c->band[ev], 0) != hipSuccess) err = RT_EHIP;
+        if (err == RT_OK)
+            err = rt_scatter_rows_async(slab_out, b0, b1, r.rowbytes, r.map(r.frame.shard), r.out, hipMemcpyDeviceToHost, cs);
+    }
+    return err;
+}
+
+// Every band of device d's shards, between the timing events.
+int render_enqueue(Render &r, uint32_t d) {
+    rt_ctx *c = r.dev[d].c;
+    int err = hipEventRecord(c->e0, c->render) == hipSuccess ? RT_OK : RT_EHIP;
+    for (uint32_t i = 0; i < r.plan.shards_of(d) && err == RT_OK; ++i) {
+        r.frame.shard = d + i * r.plan.ndev;
+        for (uint32_t b = 0; b < r.plan.nb && err == RT_OK; ++b) err = render_band(r, d, i, b);
+    }
+    if (err == RT_OK && hipEventRecord(c->e1, c->render) != hipSuccess) err = RT_EHIP;
+    return err;
+}
+
+// pageable destination: DMA into a ring of two staging bands, copied out by host threads
+// while the next band's DMA runs
+int render_drain(Render &r, uint32_t d) {
+    const RenderDev &v = r.dev[d];
+    rt_ctx *c = v.c;
+    (void)hipSetDevice(c->device);
+    const rt_bands &pl = r.plan;
+    const uint32_t nb = pl.nb, rowbytes = r.rowbytes;
+    const uint32_t total = pl.shards_of(d) * nb; // bands j = event(i, b): shard i = j / nb, band b = j % nb
+    auto stage = [&](uint32_t j) { return v.stage + (size_t)(j & 1) * pl.band * rowbytes; };
+    auto enqueue = [&](uint32_t j) -> int {
+        const uint32_t b0 = pl.row0(j % nb), b1 = pl.row1(j % nb);
+        const char *src = v.d_out + (j / nb) * r.slab_bytes + (size_t)b0 * rowbytes;
+        if (hipStreamWaitEvent(c->copy, c->band[j], 0) != hipSuccess ||
+            hipMemcpyAsync(stage(j), src, (size_t)(b1 - b0) * rowbytes, hipMemcpyDeviceToHost, c->copy) != hipSuccess ||
+            hipEventRecord(c->copied[j], c->copy) != hipSuccess)
+            return RT_EHIP;
+        return RT_OK;
+    };
     int err = RT_OK;
-    auto shards_of = [&](uint32_t d) { return (ns - d + nd - 1) / nd; }; // shards d, d + nd, ...
-    for (uint32_t d = 0; d < nd && err == RT_OK; ++d) {
-        const int dev = alias > 0 ? o.first_dev : o.first_dev + (int)d;
-        err = rt_ctx_acquire(dev, scene, n, &ctx[d]);
-        if (err != RT_OK) break;
-        rt_ctx *c = ctx[d];
-        (void)hipSetDevice(dev);
-        const uint32_t k = shards_of(d);
-        // an allocation that fails while other contexts of the device sit idle on their memory is
-        // retried once after those are trimmed (trim_idle)
-        auto retry = [&](auto &&alloc) {
-            int e = alloc();
-            if (e == RT_ENOMEM && trim_idle(dev) > 0) e = alloc();
-            return e;
-        };
-        auto buffer = [&](int which, size_t bytes, void *out) {
-            return retry([&] { return rt_ctx_device_buffer(c, which, bytes, static_cast<void **>(out)); });
-        };
-        err = buffer(0, k * rslab_bytes, &d_ren[d]);
-        d_out[d] = d_ren[d];
-        if (err == RT_OK && integer) {
-            err = buffer(2, k * slab_bytes, &d_out[d]);
-            if (err == RT_OK) err = rt_ctx_clamped(c, &d_cl[d]);
-            if (err == RT_OK && hipMemsetAsync(d_cl[d], 0, sizeof(uint64_t), c->render) != hipSuccess) err = RT_EHIP;
-        }
-        if (err == RT_OK && o.out_levels) err = buffer(1, (size_t)k * slab * width, &d_lv[d]);
-        if (err == RT_OK && !pinned) err = rt_ctx_host_buffer(c, 2 * (size_t)band * rowbytes, reinterpret_cast<void **>(&stage[d]));
-        if (err != RT_OK) break;
-        if (hipEventRecord(c->e0, c->render) != hipSuccess) err = RT_EHIP;
-        // every band's render on the render stream, its copy on the copy stream behind it
-        for (uint32_t i = 0; i < k && err == RT_OK; ++i) {
-            frame.shard = d + i * nd;
-            char *slab_out = d_out[d] + i * slab_bytes, *slab_ren = d_ren[d] + i * rslab_bytes;
-            uint8_t *slab_lv = o.out_levels ? d_lv[d] + (size_t)i * slab * width : nullptr;
-            // image rows of the shard = its slab rows [0, valid): the rest of the slab is never rendered
-            const uint32_t valid = frame.valid_rows();
-            for (uint32_t b = 0; b < nb && err == RT_OK; ++b) {
-                const uint32_t b0 = b * band, b1 = std::min(slab, b0 + band);
-                err = retry([&] { // (a failed grow launches nothing)
-                    return rt_launch_rows(c->p, frame, b0, b1, slab_ren, slab_lv, c->render, (o.flags & RT_LEVELS_HIT) ? 1 : 0);
-                });
-                // integer frame: the band's image rows quantised behind its render, before its event
-                if (err == RT_OK && integer && b0 < std::min(b1, valid))
-                    err = rt_quantize(slab_ren + (size_t)b0 * rrow, RT_OUT_F64,
-                                      (uint64_t)(std::min(b1, valid) - b0) * width * 3, o.max_value, o.precision,
-                                      slab_out + (size_t)b0 * rowbytes, d_cl[d], c->render);
-                if (err == RT_OK && hipEventRecord(c->band[i * nb + b], c->render) != hipSuccess) err = RT_EHIP;
-                if (err == RT_OK && pinned) {
-                    hipStream_t cs = ((i * nb + b) % copy_streams()) ? c->copy2 : c->copy;
-                    if (hipStreamWaitEvent(cs, c->band[i * nb + b], 0) != hipSuccess) err = RT_EHIP;
-                    if (err == RT_OK)
-                        err = rt_scatter_rows_async(slab_out, b0, b1, rowbytes, rt_shard_map{height, rb, frame.shard, ns},
-                                                    static_cast<char *>(out_rgb), hipMemcpyDeviceToHost, cs);
-                }
-            }
-        }
-        if (err == RT_OK && hipEventRecord(c->e1, c->render) != hipSuccess) err = RT_EHIP;
+    for (uint32_t j = 0; j < total && j < 2 && err == RT_OK; ++j) err = enqueue(j);
+    for (uint32_t j = 0; j < total && err == RT_OK; ++j) {
+        if (hipEventSynchronize(c->copied[j]) != hipSuccess) return RT_EHIP;
+        const uint32_t b0 = pl.row0(j % nb), b1 = pl.row1(j % nb);
+        host_scatter(stage(j), b0, b1 - b0, rowbytes, r.map(d + (j / nb) * pl.ndev), r.out);
+        if (j + 2 < total) err = enqueue(j + 2);
     }
-    // pageable destination: DMA into a ring of two staging bands, copied out by host threads
-    // while the next band's DMA runs
-    for (uint32_t d = 0; d < nd && err == RT_OK && !pinned; ++d) {
-        rt_ctx *c = ctx[d];
-        (void)hipSetDevice(c->device);
-        const uint32_t total = shards_of(d) * nb; // bands j = i * nb + b
-        auto rows_of = [&](uint32_t j, uint32_t &b0, uint32_t &b1) {
-            b0 = (j % nb) * band;
-            b1 = std::min(slab, b0 + band);
-        };
-        auto enqueue = [&](uint32_t j) -> int {
-            uint32_t b0, b1;
-            rows_of(j, b0, b1);
-            char *dst = stage[d] + (size_t)(j & 1) * band * rowbytes;
-            const char *src = d_out[d] + (j / nb) * slab_bytes + (size_t)b0 * rowbytes;
-            if (hipStreamWaitEvent(c->copy, c->band[j], 0) != hipSuccess ||
-                hipMemcpyAsync(dst, src, (size_t)(b1 - b0) * rowbytes, hipMemcpyDeviceToHost, c->copy) != hipSuccess ||
-                hipEventRecord(c->copied[j], c->copy) != hipSuccess)
-                return RT_EHIP;
-            return RT_OK;
-        };
-        for (uint32_t j = 0; j < total && j < 2 && err == RT_OK; ++j) err = enqueue(j);
-        for (uint32_t j = 0; j < total && err == RT_OK; ++j) {
-            if (hipEventSynchronize(c->copied[j]) != hipSuccess) {
-                err = RT_EHIP;
-                break;
-            }
-            uint32_t b0, b1;
-            rows_of(j, b0, b1);
-            host_scatter(stage[d] + (size_t)(j & 1) * band * rowbytes, b0, b1 - b0, rowbytes,
-                         rt_shard_map{height, rb, d + (j / nb) * nd, ns}, static_cast<char *>(out_rgb));
-            if (j + 2 < total) err = enqueue(j + 2);
-        }
-    }
-    // levels (1 byte per pixel) after the frame
-    for (uint32_t d = 0; d < nd && err == RT_OK && o.out_levels; ++d) {
-        rt_ctx *c = ctx[d];
-        (void)hipSetDevice(c->device);
-        const uint32_t k = shards_of(d);
-        std::vector<uint8_t> tmp((size_t)k * slab * width);
-        if (hipStreamSynchronize(c->render) != hipSuccess ||
-            hipMemcpy(tmp.data(), d_lv[d], tmp.size(), hipMemcpyDeviceToHost) != hipSuccess) {
-            err = RT_EHIP;
-            break;
-        }
-        for (uint32_t i = 0; i < k; ++i)
-            host_scatter(reinterpret_cast<const char *>(tmp.data()) + (size_t)i * slab * width, 0, slab, width,
-                         rt_shard_map{height, rb, d + i * nd, ns}, reinterpret_cast<char *>(o.out_levels));
-    }
+    return err;
+}
+
+// levels (1 byte per pixel) after the frame
+int render_levels(Render &r, uint32_t d) {
+    rt_ctx *c = r.dev[d].c;
+    (void)hipSetDevice(c->device);
+    const uint32_t k = r.plan.shards_of(d), slab = r.plan.slab, width = r.win.w;
+    std::vector<uint8_t> tmp((size_t)k * slab * width);
+    if (hipStreamSynchronize(c->render) != hipSuccess ||
+        hipMemcpy(tmp.data(), r.dev[d].d_lv, tmp.size(), hipMemcpyDeviceToHost) != hipSuccess)
+        return RT_EHIP;
+    for (uint32_t i = 0; i < k; ++i)
+        host_scatter(reinterpret_cast<const char *>(tmp.data()) + (size_t)i * slab * width, 0, slab, width,
+                     r.map(d + i * r.plan.ndev), reinterpret_cast<char *>(r.o.out_levels));
+    return RT_OK;
+}
+
+// Every acquired context drained and released, whatever err the stages ended with; the stats.
+int render_finish(Render &r, int err, rt_stats *stats, std::chrono::steady_clock::time_point t_begin) {
     double kms = 0;
     uint64_t clamped = 0;
-    for (uint32_t d = 0; d < nd; ++d) {
-        rt_ctx *c = ctx[d];
+    for (const RenderDev &v : r.dev) {
+        rt_ctx *c = v.c;
         if (!c) continue;
         (void)hipSetDevice(c->device);
         if (hipStreamSynchronize(c->render) != hipSuccess && err == RT_OK) err = RT_EHIP;
@@ -651,9 +662,9 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, 
         if (hipStreamSynchronize(c->copy2) != hipSuccess && err == RT_OK) err = RT_EHIP;
         float ms = 0;
         if (err == RT_OK && hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess && ms > kms) kms = ms;
-        if (err == RT_OK && d_cl[d]) {
+        if (err == RT_OK && v.d_cl) {
             uint64_t cnt = 0;
-            if (hipMemcpy(&cnt, d_cl[d], sizeof cnt, hipMemcpyDeviceToHost) != hipSuccess) err = RT_EHIP;
+            if (hipMemcpy(&cnt, v.d_cl, sizeof cnt, hipMemcpyDeviceToHost) != hipSuccess) err = RT_EHIP;
             clamped += cnt;
         }
         rt_ctx_release(c);
@@ -661,11 +672,53 @@ int rt_render(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, 
     if (stats) {
         stats->kernel_ms = kms;
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-        stats->pixels = (uint64_t)width * height;
-        stats->ndev = (int32_t)nd;
-        stats->flags = (pinned ? RT_STATS_PINNED : 0) | (clamped ? RT_STATS_CLAMPED : 0);
+        stats->pixels = (uint64_t)r.win.w * r.win.h;
+        stats->ndev = (int32_t)r.plan.ndev;
+        stats->flags = (r.pinned ? RT_STATS_PINNED : 0) | (clamped ? RT_STATS_CLAMPED : 0);
     }
     return err;
 }
 
-} // extern "C"
+} // namespace
+
+extern "C" int rt_render(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, uint32_t depth,
+                         const rt_opts *opts, void *out_rgb, rt_stats *stats) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    Render r = {scene, n, img_w, img_h, depth};
+    int err = render_plan(r, opts, out_rgb);
+    if (err != RT_OK) return err;
+    const uint32_t nd = r.plan.ndev;
+    DevGuard restore; // (the stages select each context's device themselves)
+    for (uint32_t d = 0; d < nd && err == RT_OK; ++d) {
+        err = render_acquire(r, d);
+        if (err == RT_OK) err = render_enqueue(r, d);
+    }
+    for (uint32_t d = 0; d < nd && err == RT_OK && !r.pinned; ++d) err = render_drain(r, d);
+    for (uint32_t d = 0; d < nd && err == RT_OK && r.o.out_levels; ++d) err = render_levels(r, d);
+    return render_finish(r, err, stats, t_begin);
+}
+
+int rt_file_render(rt_file_frame *ff, const char *path, int value_rc, const rt_elem *scene, uint32_t n, uint32_t img_w,
+                   uint32_t img_h, uint32_t depth, const rt_opts *opts) {
+    if (!path) return RT_EBADARG;
+    if (img_w == 0 && img_h == 0) return RT_DONE;
+    if (img_w == 0 || img_h == 0) return RT_EBADARG;
+    if (value_rc != RT_OK) return value_rc;
+    rt_opts &o = ff->o;
+    rt_opts_load(opts, &o);
+    int rc = rt_opts_window(o, img_w, img_h, &ff->win);
+    if (rc != RT_OK) return rc;
+    if (o.ndev != 1) return RT_OK;
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || o.first_dev < 0 || o.first_dev >= nd) return RT_ENODEV;
+    // the process's render context for this device: scene, streams, frame and text or sample
+    // buffers and the pinned host buffer persist across calls
+    rc = rt_ctx_acquire(o.first_dev, scene, n, &ff->ctx);
+    if (rc != RT_OK) return rc;
+    ff->dev.emplace(o.first_dev);
+    ff->st = rt_ctx_stream(ff->ctx);
+    rc = rt_ctx_device_buffer(ff->ctx, 0, ff->values() * sizeof(double), &ff->d_rgb);
+    if (rc != RT_OK) return rc;
+    return rt_launch_rows(rt_ctx_prepared(ff->ctx), rt_opts_frame(o, img_w, img_h, ff->win, depth), 0, ~0u, ff->d_rgb,
+                          nullptr, ff->st, 0);
+}

@@ -9,7 +9,10 @@
 
 #include <initializer_list>
 
+#include <optional>
+
 #include "../../include/rt_mi355x.h"
+#include "rt_format.h"
 #include "rt_shard.h"
 
 // The window an options block selects in a width x height image (o: the boundary's own copy, zero
@@ -146,9 +149,9 @@ inline int rt_hit_planes(const rt_attr_planes *planes, HitPlanes *out, int *prec
     if (planes->struct_size < offsetof(rt_attr_planes, d_albedo) + sizeof(planes->d_albedo)) return RT_EBADARG;
     const rt_attr_planes pl = *planes;
     if (!pl.d_elem && !pl.d_t && !pl.d_point && !pl.d_normal && !pl.d_albedo) return RT_EBADARG;
-    if (pl.precision != RT_OUT_F64 && pl.precision != RT_OUT_F32) return RT_EBADARG;
+    if (!rt_is_float(pl.precision)) return RT_EBADARG;
     *precision = pl.precision;
-    const uintptr_t esz = pl.precision == RT_OUT_F64 ? 8 : 4;
+    const uintptr_t esz = rt_elem_size(pl.precision);
     if ((uintptr_t)pl.d_elem % 4) return RT_EBADARG;
     for (const void *f : {pl.d_t, pl.d_point, pl.d_normal, pl.d_albedo})
         if ((uintptr_t)f % esz) return RT_EBADARG;
@@ -181,3 +184,33 @@ int rt_ctx_device_buffer(rt_ctx *c, int which, size_t bytes, void **out);
 int rt_ctx_clamped(rt_ctx *c, uint64_t **out);
 // Pinned host staging buffer of at least `bytes`, kept with the context.
 int rt_ctx_host_buffer(rt_ctx *c, size_t bytes, void **out);
+
+// ---- the two file writers' frame (rt_host.hip; rt_render_ppm_file, rt_render_rawppm_file) ----
+// The window an options block selects, rendered in binary64 into buffer 0 of its one device's
+// context, on the context's stream.  On scope exit the stream is synchronised, the context
+// released and the caller's device restored.
+struct rt_file_frame {
+    rt_opts o;        // the caller's options, loaded (rt_opts_load)
+    rt_window win;    // the file is the window's
+    rt_ctx *ctx = nullptr; // null after rt_file_render: several devices (o.ndev != 1), nothing rendered
+    hipStream_t st = nullptr;
+    void *d_rgb = nullptr;
+    std::optional<DevGuard> dev; // (not copyable, so neither is the frame)
+    ~rt_file_frame() {
+        if (!ctx) return;
+        (void)hipStreamSynchronize(st);
+        rt_ctx_release(ctx);
+    }
+    size_t values() const { return (size_t)win.w * win.h * 3; }
+    void fill(rt_stats *stats) const { // what a writer that rendered here reports
+        if (!stats) return;
+        stats->pixels = (uint64_t)win.w * win.h;
+        stats->ndev = 1;
+    }
+};
+// The writers' checks, in this order: the path; both sizes zero (RT_DONE) or one; value_rc, the
+// writer's verdict on its own arguments (RT_OK to go on); the window.  Then, for one device
+// (o.ndev == 1): the device count and first_dev (RT_ENODEV), the context, and the launch.  With
+// several devices it returns RT_OK with ff->ctx null: the writer goes through rt_render.
+int rt_file_render(rt_file_frame *ff, const char *path, int value_rc, const rt_elem *scene, uint32_t n, uint32_t img_w,
+                   uint32_t img_h, uint32_t depth, const rt_opts *opts);

@@ -239,7 +239,7 @@ size_t rt_ppm_bound(uint32_t width, uint32_t height, uint32_t max_value) {
 int rt_ppm_format(const void *d_rgb, int precision, uint32_t width, uint32_t height, uint32_t max_value, char *d_text,
                   size_t text_cap, size_t *text_len, void *stream) {
     if (!d_rgb || !d_text || !text_len) return RT_EBADARG;
-    if (precision != RT_OUT_F64 && precision != RT_OUT_F32) return RT_EBADARG;
+    if (!rt_is_float(precision)) return RT_EBADARG;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const std::string h = header_of(width, height, max_value);
     const size_t npix = (size_t)width * height;
@@ -267,10 +267,9 @@ int rt_ppm_format(const void *d_rgb, int precision, uint32_t width, uint32_t hei
     const double mv = (double)max_value;
     do {
         if (hipMemsetAsync(wide, 0, sizeof(int), st) != hipSuccess) { rc = RT_EHIP; break; }
-        if (precision == RT_OUT_F64)
-            hipLaunchKernelGGL(k_ppm_count<RT_OUT_F64>, dim3(nblk), dim3(PPM_BLOCK), 0, st, d_rgb, npix, mv, partial, wide);
-        else
-            hipLaunchKernelGGL(k_ppm_count<RT_OUT_F32>, dim3(nblk), dim3(PPM_BLOCK), 0, st, d_rgb, npix, mv, partial, wide);
+        with_format<RT_OUT_F64, RT_OUT_F32>(precision, [&](auto fmt) {
+            hipLaunchKernelGGL(k_ppm_count<decltype(fmt)::value>, dim3(nblk), dim3(PPM_BLOCK), 0, st, d_rgb, npix, mv, partial, wide);
+        });
         hipLaunchKernelGGL(k_ppm_scan, dim3(1), dim3(1024), 0, st, partial, nblk, total);
         if (hipGetLastError() != hipSuccess ||
             hipMemcpyAsync(&h_total, total, sizeof h_total, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -279,12 +278,10 @@ int rt_ppm_format(const void *d_rgb, int precision, uint32_t width, uint32_t hei
         if (h_wide) { rc = RT_ERANGE; break; }
         if (h_total >= (1ull << 32) || h.size() + h_total > text_cap) { rc = RT_ETOOBIG; break; }
         if (hipMemcpyAsync(d_text, h.data(), h.size(), hipMemcpyHostToDevice, st) != hipSuccess) { rc = RT_EHIP; break; }
-        if (precision == RT_OUT_F64)
-            hipLaunchKernelGGL(k_ppm_write<RT_OUT_F64>, dim3(nblk), dim3(PPM_BLOCK), 0, st, d_rgb, npix, mv, partial,
+        with_format<RT_OUT_F64, RT_OUT_F32>(precision, [&](auto fmt) {
+            hipLaunchKernelGGL(k_ppm_write<decltype(fmt)::value>, dim3(nblk), dim3(PPM_BLOCK), 0, st, d_rgb, npix, mv, partial,
                                d_text, h.size());
-        else
-            hipLaunchKernelGGL(k_ppm_write<RT_OUT_F32>, dim3(nblk), dim3(PPM_BLOCK), 0, st, d_rgb, npix, mv, partial,
-                               d_text, h.size());
+        });
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = RT_EHIP; break; }
         *text_len = h.size() + (size_t)h_total;
     } while (0);
@@ -295,23 +292,16 @@ int rt_ppm_format(const void *d_rgb, int precision, uint32_t width, uint32_t hei
 
 int rt_render_ppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, uint32_t depth,
                        const rt_opts *opts, uint32_t max_value, const char *path, rt_stats *stats) {
-    uint32_t width = img_w, height = img_h; // the window's from the window check on: the file is the window's
-    if (!path) return RT_EBADARG;
-    if (width == 0 && height == 0) return RT_DONE;
-    if (width == 0 || height == 0) return RT_EBADARG;
-    rt_opts o;
-    rt_opts_load(opts, &o);
-    o.precision = RT_OUT_F64; // the reference's values: the text is byte-exact
-    o.out_levels = nullptr;
-    FILE *f = nullptr;
-    rt_window win;
-    int rc = rt_opts_window(o, img_w, img_h, &win);
+    rt_file_frame ff;
+    int rc = rt_file_render(&ff, path, RT_OK, scene, n, img_w, img_h, depth, opts);
     if (rc != RT_OK) return rc;
-    width = win.w;
-    height = win.h;
-    if (o.ndev != 1) { // several devices: rt_render assembles the frame on the host
-        std::vector<double> img((size_t)width * height * 3);
-        rc = rt_render(scene, n, img_w, img_h, depth, &o, img.data(), stats);
+    const uint32_t width = ff.win.w, height = ff.win.h; // the file is the window's
+    FILE *f = nullptr;
+    if (!ff.ctx) { // several devices: rt_render assembles the frame on the host
+        ff.o.precision = RT_OUT_F64; // the reference's values: the text is byte-exact
+        ff.o.out_levels = nullptr;
+        std::vector<double> img(ff.values());
+        rc = rt_render(scene, n, img_w, img_h, depth, &ff.o, img.data(), stats);
         if (rc != RT_OK) return rc;
         f = std::fopen(path, "wb");
         if (!f) return RT_EBADARG;
@@ -319,29 +309,15 @@ int rt_render_ppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_
         std::fclose(f);
         return rc;
     }
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || o.first_dev < 0 || o.first_dev >= nd) return RT_ENODEV;
-    // the process's render context for this device (rt_host.hip): scene, streams, frame and text
-    // buffers and the pinned host buffer persist across calls
-    rt_ctx *ctx = nullptr;
-    rc = rt_ctx_acquire(o.first_dev, scene, n, &ctx);
-    if (rc != RT_OK) return rc;
-    DevGuard g(o.first_dev);
-    const rt_frame frame = rt_opts_frame(o, img_w, img_h, win, depth);
-    const size_t frame_bytes = (size_t)width * height * 3 * sizeof(double);
     const size_t cap = rt_ppm_bound(width, height, max_value);
-    void *d_rgb = nullptr, *d_text = nullptr, *h_text = nullptr;
-    hipStream_t st = rt_ctx_stream(ctx);
+    void *d_text = nullptr, *h_text = nullptr;
     size_t len = 0;
     do {
-        if ((rc = rt_ctx_device_buffer(ctx, 0, frame_bytes, &d_rgb)) != RT_OK) break;
-        if ((rc = rt_ctx_device_buffer(ctx, 2, cap, &d_text)) != RT_OK) break;
-        rc = rt_launch_rows(rt_ctx_prepared(ctx), frame, 0, ~0u, d_rgb, nullptr, st, 0);
-        if (rc != RT_OK) break;
-        rc = rt_ppm_format(d_rgb, RT_OUT_F64, width, height, max_value, static_cast<char *>(d_text), cap, &len, st);
+        if ((rc = rt_ctx_device_buffer(ff.ctx, 2, cap, &d_text)) != RT_OK) break;
+        rc = rt_ppm_format(ff.d_rgb, RT_OUT_F64, width, height, max_value, static_cast<char *>(d_text), cap, &len, ff.st);
         if (rc == RT_ERANGE) { // a colour BEAM would print as a bignum: format on the host
-            std::vector<double> img((size_t)width * height * 3);
-            if (hipMemcpy(img.data(), d_rgb, frame_bytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = RT_EHIP; break; }
+            std::vector<double> img(ff.values());
+            if (hipMemcpy(img.data(), ff.d_rgb, img.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { rc = RT_EHIP; break; }
             f = std::fopen(path, "wb");
             if (!f) { rc = RT_EBADARG; break; }
             rc = host_ppm(img.data(), width, height, max_value, f);
@@ -349,20 +325,15 @@ int rt_render_ppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_
         }
         if (rc != RT_OK) break;
         // the text to pinned memory by DMA, written to the file from there
-        if ((rc = rt_ctx_host_buffer(ctx, len ? len : 1, &h_text)) != RT_OK) break;
-        if (hipMemcpyAsync(h_text, d_text, len, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = RT_EHIP; break; }
+        if ((rc = rt_ctx_host_buffer(ff.ctx, len ? len : 1, &h_text)) != RT_OK) break;
+        if (hipMemcpyAsync(h_text, d_text, len, hipMemcpyDeviceToHost, ff.st) != hipSuccess ||
+            hipStreamSynchronize(ff.st) != hipSuccess) { rc = RT_EHIP; break; }
         f = std::fopen(path, "wb");
         if (!f) { rc = RT_EBADARG; break; }
         if (std::fwrite(h_text, 1, len, f) != len) rc = RT_EBADARG;
     } while (0);
     if (f) std::fclose(f);
-    (void)hipStreamSynchronize(st);
-    rt_ctx_release(ctx);
-    if (stats && rc == RT_OK) {
-        stats->pixels = (uint64_t)width * height;
-        stats->ndev = 1;
-    }
+    if (rc == RT_OK) ff.fill(stats);
     return rc;
 }
 

@@ -166,12 +166,10 @@ void launch_quant(const void *in, void *out, uint64_t n, uint32_t head, bool vec
     const uint64_t nvec = (n - head) / QUANT_V;
     const uint64_t want = (nvec + QUANT_BLOCK - 1) / QUANT_BLOCK;
     const unsigned grid = (unsigned)(want < 1 ? 1 : want > QUANT_MAX_BLOCKS ? QUANT_MAX_BLOCKS : want);
-    if (vec)
-        hipLaunchKernelGGL((k_quant<TIN, TOUT, true>), dim3(grid), dim3(QUANT_BLOCK), 0, st,
+    with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL((k_quant<TIN, TOUT, decltype(v)::value>), dim3(grid), dim3(QUANT_BLOCK), 0, st,
                            static_cast<const TIN *>(in), static_cast<TOUT *>(out), n, head, nvec, maxv, maxi, clamped);
-    else
-        hipLaunchKernelGGL((k_quant<TIN, TOUT, false>), dim3(grid), dim3(QUANT_BLOCK), 0, st,
-                           static_cast<const TIN *>(in), static_cast<TOUT *>(out), n, head, nvec, maxv, maxi, clamped);
+    });
 }
 
 // One value of a resolved frame: the mean as TOUT, quantised when TOUT is an integer.
@@ -265,12 +263,10 @@ void launch_resolve(const double *in, void *out, uint64_t n, uint32_t head, bool
     const uint64_t nvec = (n - head) / QUANT_V;
     const uint64_t want = (nvec + QUANT_BLOCK - 1) / QUANT_BLOCK;
     const unsigned grid = (unsigned)(want < 1 ? 1 : want > QUANT_MAX_BLOCKS ? QUANT_MAX_BLOCKS : want);
-    if (vec)
-        hipLaunchKernelGGL((k_resolve<TOUT, true>), dim3(grid), dim3(QUANT_BLOCK), 0, st, in, static_cast<TOUT *>(out), n,
-                           head, nvec, cnt, maxv, maxi, clamped);
-    else
-        hipLaunchKernelGGL((k_resolve<TOUT, false>), dim3(grid), dim3(QUANT_BLOCK), 0, st, in, static_cast<TOUT *>(out), n,
-                           head, nvec, cnt, maxv, maxi, clamped);
+    with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL((k_resolve<TOUT, decltype(v)::value>), dim3(grid), dim3(QUANT_BLOCK), 0, st, in,
+                           static_cast<TOUT *>(out), n, head, nvec, cnt, maxv, maxi, clamped);
+    });
 }
 
 void p6_header(char h[64], uint32_t W, uint32_t H, uint32_t maxv) { std::snprintf(h, 64, "P6\n%u %u\n%u\n", W, H, maxv); }
@@ -304,11 +300,11 @@ extern "C" {
 int rt_quantize(const void *d_rgb, int precision, uint64_t n_values, uint32_t max_value, int out_format, void *d_out,
                 uint64_t *d_clamped, void *stream) {
     if (!d_rgb || !d_out) return RT_EBADARG;
-    if (precision != RT_OUT_F64 && precision != RT_OUT_F32) return RT_EBADARG;
-    if (out_format != RT_OUT_U8 && out_format != RT_OUT_U16) return RT_EBADARG;
+    if (!rt_is_float(precision)) return RT_EBADARG;
+    if (!rt_is_int(out_format)) return RT_EBADARG;
     if (max_value == 0) return RT_EBADARG;
-    if (max_value > (out_format == RT_OUT_U8 ? 255u : (uint32_t)RT_MAX_INT_VALUE)) return RT_ETOOBIG;
-    const size_t isz = precision == RT_OUT_F64 ? 8 : 4, osz = out_format == RT_OUT_U8 ? 1 : 2;
+    if (max_value > rt_max_value_of(out_format)) return RT_ETOOBIG;
+    const size_t isz = rt_elem_size(precision), osz = rt_elem_size(out_format);
     if ((uintptr_t)d_rgb % isz || (uintptr_t)d_out % osz || (uintptr_t)d_clamped % 8) return RT_EBADARG;
     if (n_values == 0) return RT_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -318,14 +314,12 @@ int rt_quantize(const void *d_rgb, int precision, uint64_t n_values, uint32_t ma
     const bool vec = ((uintptr_t)d_rgb + head * isz) % 16 == 0;
     const double maxv = (double)max_value;
     unsigned long long *cl = reinterpret_cast<unsigned long long *>(d_clamped);
-    if (precision == RT_OUT_F64 && out_format == RT_OUT_U8)
-        launch_quant<double, uint8_t>(d_rgb, d_out, n_values, (uint32_t)head, vec, maxv, max_value, cl, st);
-    else if (precision == RT_OUT_F64)
-        launch_quant<double, uint16_t>(d_rgb, d_out, n_values, (uint32_t)head, vec, maxv, max_value, cl, st);
-    else if (out_format == RT_OUT_U8)
-        launch_quant<float, uint8_t>(d_rgb, d_out, n_values, (uint32_t)head, vec, maxv, max_value, cl, st);
-    else
-        launch_quant<float, uint16_t>(d_rgb, d_out, n_values, (uint32_t)head, vec, maxv, max_value, cl, st);
+    with_format<RT_OUT_F64, RT_OUT_F32>(precision, [&](auto in) {
+        with_format<RT_OUT_U8, RT_OUT_U16>(out_format, [&](auto out) {
+            launch_quant<typename decltype(in)::type, typename decltype(out)::type>(d_rgb, d_out, n_values, (uint32_t)head, vec,
+                                                                                    maxv, max_value, cl, st);
+        });
+    });
     QCHK(hipGetLastError());
     return RT_OK;
 }
@@ -333,14 +327,13 @@ int rt_quantize(const void *d_rgb, int precision, uint64_t n_values, uint32_t ma
 int rt_resolve(const double *d_sum, uint64_t n_values, uint32_t samples, int out_format, uint32_t max_value, void *d_out,
                uint64_t *d_clamped, void *stream) {
     if (!d_sum || !d_out) return RT_EBADARG;
-    if (out_format != RT_OUT_F64 && out_format != RT_OUT_F32 && out_format != RT_OUT_U8 && out_format != RT_OUT_U16)
-        return RT_EBADARG;
+    if (!rt_format_ok(out_format)) return RT_EBADARG;
     if (samples == 0) return RT_EBADARG;
     if (samples > RT_MAX_SPP) return RT_ETOOBIG;
-    const bool integer = out_format == RT_OUT_U8 || out_format == RT_OUT_U16;
+    const bool integer = rt_is_int(out_format);
     if (integer && max_value == 0) return RT_EBADARG;
-    if (integer && max_value > (out_format == RT_OUT_U8 ? 255u : (uint32_t)RT_MAX_INT_VALUE)) return RT_ETOOBIG;
-    const size_t osz = out_format == RT_OUT_F64 ? 8 : out_format == RT_OUT_F32 ? 4 : out_format == RT_OUT_U16 ? 2 : 1;
+    if (integer && max_value > rt_max_value_of(out_format)) return RT_ETOOBIG;
+    const size_t osz = rt_elem_size(out_format);
     if ((uintptr_t)d_sum % 8 || (uintptr_t)d_out % osz || (uintptr_t)d_clamped % 8) return RT_EBADARG;
     if (n_values == 0) return RT_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -351,82 +344,53 @@ int rt_resolve(const double *d_sum, uint64_t n_values, uint32_t samples, int out
     const double cnt = (double)samples, maxv = integer ? (double)max_value : 0.0;
     const unsigned maxi = integer ? max_value : 0u;
     unsigned long long *cl = reinterpret_cast<unsigned long long *>(d_clamped);
-    if (out_format == RT_OUT_F64)
-        launch_resolve<double>(d_sum, d_out, n_values, (uint32_t)head, vec, cnt, maxv, maxi, cl, st);
-    else if (out_format == RT_OUT_F32)
-        launch_resolve<float>(d_sum, d_out, n_values, (uint32_t)head, vec, cnt, maxv, maxi, cl, st);
-    else if (out_format == RT_OUT_U8)
-        launch_resolve<uint8_t>(d_sum, d_out, n_values, (uint32_t)head, vec, cnt, maxv, maxi, cl, st);
-    else
-        launch_resolve<uint16_t>(d_sum, d_out, n_values, (uint32_t)head, vec, cnt, maxv, maxi, cl, st);
+    with_format(out_format, [&](auto out) {
+        launch_resolve<typename decltype(out)::type>(d_sum, d_out, n_values, (uint32_t)head, vec, cnt, maxv, maxi, cl, st);
+    });
     QCHK(hipGetLastError());
     return RT_OK;
 }
 
 int rt_render_rawppm_file(const rt_elem *scene, uint32_t n, uint32_t img_w, uint32_t img_h, uint32_t depth,
                           const rt_opts *opts, uint32_t max_value, const char *path, rt_stats *stats) {
-    uint32_t width = img_w, height = img_h; // the window's from the window check on: the file is the window's
-    if (!path) return RT_EBADARG;
-    if (width == 0 && height == 0) return RT_DONE;
-    if (width == 0 || height == 0) return RT_EBADARG;
-    if (max_value == 0) return RT_EBADARG;
-    if (max_value > RT_MAX_INT_VALUE) return RT_ETOOBIG;
-    rt_opts o;
-    rt_opts_load(opts, &o);
-    rt_window win;
-    int rc = rt_opts_window(o, img_w, img_h, &win);
+    const int value_rc = max_value == 0 ? RT_EBADARG : max_value > RT_MAX_INT_VALUE ? RT_ETOOBIG : RT_OK;
+    rt_file_frame ff;
+    int rc = rt_file_render(&ff, path, value_rc, scene, n, img_w, img_h, depth, opts);
     if (rc != RT_OK) return rc;
-    width = win.w;
-    height = win.h;
-    const int fmt = max_value > 255 ? RT_OUT_U16 : RT_OUT_U8;
-    const size_t osz = fmt == RT_OUT_U16 ? 2 : 1;
-    const size_t nval = (size_t)width * height * 3;
-    o.precision = fmt;
-    o.max_value = max_value;
-    o.out_levels = nullptr;
-    if (o.ndev != 1) { // several devices: rt_render assembles the integer frame on the host
-        std::vector<unsigned char> img(nval * osz);
+    const uint32_t width = ff.win.w, height = ff.win.h; // the file is the window's
+    const int fmt = max_value > rt_max_value_of(RT_OUT_U8) ? RT_OUT_U16 : RT_OUT_U8;
+    const size_t nval = ff.values(), bytes = nval * rt_elem_size(fmt);
+    if (!ff.ctx) { // several devices: rt_render assembles the integer frame on the host
+        ff.o.precision = fmt;
+        ff.o.max_value = max_value;
+        ff.o.out_levels = nullptr;
+        std::vector<unsigned char> img(bytes);
         rt_stats st;
         std::memset(&st, 0, sizeof st);
-        rc = rt_render(scene, n, img_w, img_h, depth, &o, img.data(), &st);
+        rc = rt_render(scene, n, img_w, img_h, depth, &ff.o, img.data(), &st);
         if (rc != RT_OK) return rc;
         if (stats) *stats = st;
         if (st.flags & RT_STATS_CLAMPED) return RT_ERANGE; // P3 would print a negative number
         return write_p6(path, width, height, max_value, img.data());
     }
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || o.first_dev < 0 || o.first_dev >= nd) return RT_ENODEV;
-    rt_ctx *ctx = nullptr;
-    rc = rt_ctx_acquire(o.first_dev, scene, n, &ctx);
-    if (rc != RT_OK) return rc;
-    DevGuard g(o.first_dev);
-    const rt_frame frame = rt_opts_frame(o, img_w, img_h, win, depth);
-    void *d_rgb = nullptr, *d_int = nullptr, *h_int = nullptr;
+    void *d_int = nullptr, *h_int = nullptr;
     uint64_t *d_clamped = nullptr;
     uint64_t clamped = 0;
-    hipStream_t st = rt_ctx_stream(ctx);
+    hipStream_t st = ff.st;
     do {
-        if ((rc = rt_ctx_device_buffer(ctx, 0, nval * sizeof(double), &d_rgb)) != RT_OK) break;
-        if ((rc = rt_ctx_device_buffer(ctx, 2, nval * osz, &d_int)) != RT_OK) break;
-        if ((rc = rt_ctx_clamped(ctx, &d_clamped)) != RT_OK) break;
-        if ((rc = rt_ctx_host_buffer(ctx, nval * osz, &h_int)) != RT_OK) break;
+        if ((rc = rt_ctx_device_buffer(ff.ctx, 2, bytes, &d_int)) != RT_OK) break;
+        if ((rc = rt_ctx_clamped(ff.ctx, &d_clamped)) != RT_OK) break;
+        if ((rc = rt_ctx_host_buffer(ff.ctx, bytes, &h_int)) != RT_OK) break;
         if (hipMemsetAsync(d_clamped, 0, sizeof clamped, st) != hipSuccess) { rc = RT_EHIP; break; }
-        rc = rt_launch_rows(rt_ctx_prepared(ctx), frame, 0, ~0u, d_rgb, nullptr, st, 0);
-        if (rc != RT_OK) break;
-        if ((rc = rt_quantize(d_rgb, RT_OUT_F64, nval, max_value, fmt, d_int, d_clamped, st)) != RT_OK) break;
+        if ((rc = rt_quantize(ff.d_rgb, RT_OUT_F64, nval, max_value, fmt, d_int, d_clamped, st)) != RT_OK) break;
         // the samples and the counter to pinned memory by DMA; the file is written from there
-        if (hipMemcpyAsync(h_int, d_int, nval * osz, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        if (hipMemcpyAsync(h_int, d_int, bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipMemcpyAsync(&clamped, d_clamped, sizeof clamped, hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess) { rc = RT_EHIP; break; }
         if (clamped) { rc = RT_ERANGE; break; } // before the path is opened: no file
         rc = write_p6(path, width, height, max_value, h_int);
     } while (0);
-    (void)hipStreamSynchronize(st);
-    rt_ctx_release(ctx);
-    if (stats && (rc == RT_OK || rc == RT_ERANGE)) {
-        stats->pixels = (uint64_t)width * height;
-        stats->ndev = 1;
-    }
+    if (rc == RT_OK || rc == RT_ERANGE) ff.fill(stats);
     return rc;
 }
 

@@ -1014,7 +1014,7 @@ int wave_pass(rt_prepared *p, const WavePlan &pl, const rt_frame &f, int row0, v
     ps.rows = std::min(pl.pass_rows, pl.row_end - row0);
     const int ntiles = ps.ntiles = pl.tiles_x * ((ps.rows + TILE - 1) / TILE);
     const size_t off = (size_t)row0 * W;
-    ps.o = static_cast<char *>(out) + off * 3 * (PREC == RT_OUT_F64 ? 8 : 4);
+    ps.o = static_cast<char *>(out) + off * 3 * sizeof(typename rt_format<PREC>::type);
     ps.lv0 = levels ? levels + off : nullptr;
     ps.lv = pl.count_levels ? ps.lv0 : nullptr;
     double *acc_p = smp.acc ? smp.acc + off * 3 : nullptr;
@@ -1216,7 +1216,7 @@ int launch_sample_passes(rt_prepared *p, const rt_frame &f, const SampleBand &b,
         if (rc != RT_OK) return rc;
         if (single) continue;
         // keep: k_accum told of a frame one sample longer folds and keeps the sum, and never reads its output
-        void *dst = b.keep ? nullptr : static_cast<char *>(b.out) + e0 * (f.precision == RT_OUT_F64 ? 8 : 4);
+        void *dst = b.keep ? nullptr : static_cast<char *>(b.out) + e0 * rt_elem_size(f.precision);
         with_int<RT_OUT_F64, RT_OUT_F32>(f.precision, [&](auto prec) {
             p->launched.note(LaunchRecord::ACCUM, {decltype(prec)::value});
             hipLaunchKernelGGL(k_accum<decltype(prec)::value>, dim3(blocks), dim3(256), 0, st, n, slab + e0, b.acc + e0, dst,
@@ -1369,10 +1369,8 @@ int rt_launch_samples(rt_prepared *p, uint32_t width, uint32_t height, uint32_t 
 int rt_unshard(const void *d_slabs, uint32_t width, uint32_t height, uint32_t row_block, uint32_t nshards,
                int precision, void *d_image, void *stream) {
     if (!d_slabs || !d_image || width == 0 || height == 0 || row_block == 0 || nshards == 0) return RT_EBADARG;
-    if (precision != RT_OUT_F64 && precision != RT_OUT_F32 && precision != RT_OUT_U8 && precision != RT_OUT_U16)
-        return RT_EBADARG;
-    uint32_t esz = precision == RT_OUT_F64 ? 8 : precision == RT_OUT_F32 ? 4 : precision == RT_OUT_U16 ? 2 : 1;
-    uint32_t rowbytes = width * 3 * esz;
+    if (!rt_format_ok(precision)) return RT_EBADARG;
+    uint32_t rowbytes = width * 3 * (uint32_t)rt_elem_size(precision);
     const uint32_t slab = rt_shard_slab_rows(height, row_block, nshards);
     uint64_t slab_bytes = (uint64_t)slab * rowbytes;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

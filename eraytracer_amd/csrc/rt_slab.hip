@@ -32,6 +32,7 @@
 #include <cstdio>
 
 #include "../../include/rt_mi355x.h"
+#include "rt_format.h"
 #include "rt_shard.h"
 
 namespace {
@@ -388,9 +389,7 @@ __global__ __launch_bounds__(SLAB_BLOCK) void k_unpack_int(ShardPtrs sp, uint64_
 
 bool args_ok(uint32_t width, uint32_t height, uint32_t row_block, uint32_t nshards, int precision) {
     if (width == 0 || height == 0 || row_block == 0 || nshards == 0 || nshards > RT_MAX_SHARDS) return false;
-    if (precision != RT_OUT_F64 && precision != RT_OUT_F32 && precision != RT_OUT_U8 && precision != RT_OUT_U16)
-        return false;
-    return true;
+    return rt_format_ok(precision);
 }
 
 // an integer slab, values buffer or image is aligned to its sample (the float kernels leave their
@@ -399,11 +398,10 @@ bool int_aligned(const void *p, int precision) {
     return precision != RT_OUT_U16 || (reinterpret_cast<uintptr_t>(p) & 1) == 0;
 }
 
-bool is_int(int precision) { return precision == RT_OUT_U8 || precision == RT_OUT_U16; }
-
-// rt_slab_pack's three kernels on an integer slab (T = uint8_t / uint16_t): one pixel per thread
+// rt_slab_pack's three kernels on a slab of T, the unsigned integer of the format's element size
+// (a float slab goes as bit patterns): one pixel per thread
 template <typename T>
-int pack_int(const void *d_slab, const Layout &l, uint64_t valid_px, unsigned char *h, void *d_values, hipStream_t st) {
+int pack(const void *d_slab, const Layout &l, uint64_t valid_px, unsigned char *h, void *d_values, hipStream_t st) {
     uint32_t *off = reinterpret_cast<uint32_t *>(h + HDR_OFFS);
     uint64_t *mask = reinterpret_cast<uint64_t *>(h + l.mask_at);
     const dim3 grid((unsigned)l.nblk), blk(SLAB_BLOCK);
@@ -417,24 +415,32 @@ int pack_int(const void *d_slab, const Layout &l, uint64_t valid_px, unsigned ch
     return RT_OK;
 }
 
-// rt_slab_unpack of integer shards: 48 bytes per thread and 16-byte stores when every image row
-// starts on a multiple of 16 bytes and holds whole threads (a 16-byte aligned image whose width is
-// a multiple of 16 pixels of u8 / 8 of u16: 48 bytes), else the element-wise kernel
+// rt_slab_unpack's choice between its three kernels.  The wide one of the format decodes G pixels
+// per thread with 16-byte stores, when every image row starts on a multiple of 16 bytes and holds
+// whole threads: a 16-byte aligned image whose width is a multiple of G.
+//   float shards: k_unpack4, G = 4 pixels (48 or 96 bytes);
+//   integer shards: k_unpack_int, 48 bytes per thread (G = 16 pixels of u8, 8 of u16).
+// Any other image (a view into a larger buffer) takes the element-wise kernel, k_unpack.
 template <typename T>
-int unpack_int(const ShardPtrs &sp, const Layout &l, uint32_t width, uint32_t height, uint32_t row_block,
-               uint32_t nshards, void *d_image, hipStream_t st) {
-    constexpr uint32_t G = INT_BYTES / (3 * sizeof(T));
+int unpack(const ShardPtrs &sp, const Layout &l, uint32_t width, uint32_t height, uint32_t row_block, uint32_t nshards,
+           void *d_image, hipStream_t st) {
+    constexpr bool INT = sizeof(T) < 4;
+    constexpr uint32_t G = INT ? INT_BYTES / (3 * sizeof(T)) : UNPACK_PX;
     const bool wide = width % G == 0 && (reinterpret_cast<uintptr_t>(d_image) & 15) == 0;
     const uint32_t per_wg = wide ? SLAB_BLOCK * G : SLAB_BLOCK;
     const uint32_t ncol = (uint32_t)(((uint64_t)width + per_wg - 1) / per_wg);
     const uint64_t nblocks = (uint64_t)ncol * height;
     if (nblocks >= (1ull << 31)) return RT_ETOOBIG;
-    if (wide)
-        hipLaunchKernelGGL(k_unpack_int<T>, dim3((unsigned)nblocks), dim3(SLAB_BLOCK), 0, st, sp, l.mask_at, l.px, width,
-                           ncol, row_block, nshards, static_cast<T *>(d_image));
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)nblocks), dim3(SLAB_BLOCK), 0, st, sp, l.mask_at, l.px, width, ncol,
+                           row_block, nshards, static_cast<T *>(d_image));
+    };
+    if (!wide)
+        launch(k_unpack<T>);
+    else if constexpr (INT)
+        launch(k_unpack_int<T>);
     else
-        hipLaunchKernelGGL(k_unpack<T>, dim3((unsigned)nblocks), dim3(SLAB_BLOCK), 0, st, sp, l.mask_at, l.px, width,
-                           ncol, row_block, nshards, static_cast<T *>(d_image));
+        launch(k_unpack4<T>);
     SLABCHK(hipGetLastError());
     return RT_OK;
 }
@@ -455,34 +461,12 @@ int rt_slab_pack(const void *d_slab, uint32_t width, uint32_t height, uint32_t r
         return RT_EBADARG;
     const Layout l = layout(width, rt_shard_rows(height, row_block, nshards));
     if (l.px >= (1ull << 32)) return RT_ETOOBIG;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    unsigned char *h = static_cast<unsigned char *>(d_header);
-    uint64_t *count = reinterpret_cast<uint64_t *>(h);
-    uint32_t *off = reinterpret_cast<uint32_t *>(h + HDR_OFFS);
-    uint64_t *mask = reinterpret_cast<uint64_t *>(h + l.mask_at);
-    const dim3 grid((unsigned)l.nblk), blk(SLAB_BLOCK);
     // the slab rows inside the image are a prefix of the slab (rt_shard.h)
     const uint64_t valid_px = (uint64_t)rt_shard_valid_rows(height, row_block, shard, nshards) * width;
-    if (is_int(precision))
-        return precision == RT_OUT_U8 ? pack_int<uint8_t>(d_slab, l, valid_px, h, d_values, st)
-                                      : pack_int<uint16_t>(d_slab, l, valid_px, h, d_values, st);
-    if (precision == RT_OUT_F32)
-        hipLaunchKernelGGL(k_mask<uint32_t>, grid, blk, 0, st, static_cast<const uint32_t *>(d_slab), valid_px, off,
-                           mask);
-    else
-        hipLaunchKernelGGL(k_mask<uint64_t>, grid, blk, 0, st, static_cast<const uint64_t *>(d_slab), valid_px, off,
-                           mask);
-    SLABCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, off, l.nblk, count);
-    SLABCHK(hipGetLastError());
-    if (precision == RT_OUT_F32)
-        hipLaunchKernelGGL(k_compact<uint32_t>, grid, blk, 0, st, static_cast<const uint32_t *>(d_slab), l.px, off,
-                           mask, static_cast<uint32_t *>(d_values));
-    else
-        hipLaunchKernelGGL(k_compact<uint64_t>, grid, blk, 0, st, static_cast<const uint64_t *>(d_slab), l.px, off,
-                           mask, static_cast<uint64_t *>(d_values));
-    SLABCHK(hipGetLastError());
-    return RT_OK;
+    return with_format(precision, [&](auto fmt) {
+        return pack<typename decltype(fmt)::bits>(d_slab, l, valid_px, static_cast<unsigned char *>(d_header), d_values,
+                                                  reinterpret_cast<hipStream_t>(stream));
+    });
 }
 
 int rt_slab_unpack(const void *const *d_headers, const void *const *d_values, uint32_t width, uint32_t height,
@@ -498,38 +482,10 @@ int rt_slab_unpack(const void *const *d_headers, const void *const *d_values, ui
         sp.hdr[s] = static_cast<const unsigned char *>(d_headers[s]);
         sp.vals[s] = d_values[s];
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (is_int(precision))
-        return precision == RT_OUT_U8 ? unpack_int<uint8_t>(sp, l, width, height, row_block, nshards, d_image, st)
-                                      : unpack_int<uint16_t>(sp, l, width, height, row_block, nshards, d_image, st);
-    // 4 pixels per thread, 16-byte stores: every row of a 16-byte aligned image starts on a multiple
-    // of 16 bytes (4 pixels are 48 or 96 bytes); any other image (a view into a larger buffer)
-    // takes the element-wise kernel
-    if (width % UNPACK_PX == 0 && (reinterpret_cast<uintptr_t>(d_image) & 15) == 0) {
-        const uint32_t ncol = (width + SLAB_BLOCK * UNPACK_PX - 1) / (SLAB_BLOCK * UNPACK_PX);
-        const uint64_t nblocks = (uint64_t)ncol * height;
-        if (nblocks >= (1ull << 31)) return RT_ETOOBIG;
-        if (precision == RT_OUT_F32)
-            hipLaunchKernelGGL(k_unpack4<uint32_t>, dim3((unsigned)nblocks), dim3(SLAB_BLOCK), 0, st, sp, l.mask_at,
-                               l.px, width, ncol, row_block, nshards, static_cast<uint32_t *>(d_image));
-        else
-            hipLaunchKernelGGL(k_unpack4<uint64_t>, dim3((unsigned)nblocks), dim3(SLAB_BLOCK), 0, st, sp, l.mask_at,
-                               l.px, width, ncol, row_block, nshards, static_cast<uint64_t *>(d_image));
-        SLABCHK(hipGetLastError());
-        return RT_OK;
-    }
-    const uint32_t ncol = (width + SLAB_BLOCK - 1) / SLAB_BLOCK;
-    const uint64_t nblocks = (uint64_t)ncol * height;
-    if (nblocks >= (1ull << 31)) return RT_ETOOBIG;
-    const dim3 grid((unsigned)nblocks);
-    if (precision == RT_OUT_F32)
-        hipLaunchKernelGGL(k_unpack<uint32_t>, grid, dim3(SLAB_BLOCK), 0, st, sp, l.mask_at, l.px, width, ncol, row_block,
-                           nshards, static_cast<uint32_t *>(d_image));
-    else
-        hipLaunchKernelGGL(k_unpack<uint64_t>, grid, dim3(SLAB_BLOCK), 0, st, sp, l.mask_at, l.px, width, ncol, row_block,
-                           nshards, static_cast<uint64_t *>(d_image));
-    SLABCHK(hipGetLastError());
-    return RT_OK;
+    return with_format(precision, [&](auto fmt) {
+        return unpack<typename decltype(fmt)::bits>(sp, l, width, height, row_block, nshards, d_image,
+                                                    reinterpret_cast<hipStream_t>(stream));
+    });
 }
 
 } // extern "C"

@@ -219,3 +219,41 @@ def test_levels_hit_mask(name, w, h, d, spp):
     assert np.array_equal(img2.view(np.int64), plain.view(np.int64))
     assert set(np.unique(mask).tolist()) <= {0, 1}
     assert np.array_equal(mask, (lv > 0).astype(np.uint8))
+
+
+_SHARD_BANDS_CHILD = r"""
+import numpy as np
+from eraytracer_amd import _native as N, records
+from eraytracer_amd.raytracer import render
+w, h, d, sc = 1024, 300, 2, records.scene()
+for prec, dt in (('f64', np.float64), ('u8', np.uint8)):
+    for rb in (16, 5):
+        one = render(w, h, sc, d, precision=prec, row_block=rb)
+        for out in (None, N.pinned_empty((h, w, 3), dt)):
+            st = {}
+            got = render(w, h, sc, d, precision=prec, row_block=rb, nshards=3, out=out, stats=st)
+            assert st['pinned'] is (out is not None)
+            assert np.array_equal(got.view(np.uint8), one.view(np.uint8)), (prec, rb, out is None)
+print('ok')
+"""
+
+
+def test_several_shards_of_several_bands_on_one_device():
+    """Three shards on one device, each slab cut into several bands (RT_BAND_MB=1, read once per
+    process: a child): band b of the device's i-th shard has event i * nb + b, and the pageable ring
+    finds band j's shard as j / nb.  1024x300 in binary64 is 24576 bytes a row, so bands of 32 rows
+    with 16-row blocks (slabs of 112 rows: 4 bands) and of lcm(5, 16) = 80 rows with 5-row blocks
+    (slabs of 100 rows: 2 bands); f64 and u8 frames into pinned and pageable memory equal the
+    one-shard frame of the same call bit for bit."""
+    import os
+    import subprocess
+    import sys
+    for rb, slab, band, nb in ((16, 112, 32, 4), (5, 100, 80, 2)):
+        gran = rb * 16 // np.gcd(rb, 16)
+        assert -(-(-(-300 // rb)) // 3) * rb == slab and max((1 << 20) // 24576 // gran * gran, gran) == band
+        assert -(-slab // band) == nb
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    e = dict(os.environ, PYTHONPATH=root, RT_BAND_MB="1")
+    r = subprocess.run([sys.executable, "-c", _SHARD_BANDS_CHILD], cwd=root, env=e, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0 and "ok" in r.stdout.split(), r.stdout + r.stderr

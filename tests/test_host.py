@@ -151,3 +151,25 @@ def test_shard_mapping_under_host_sanitizers(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr
     assert int(r.stdout) == 70 * 6 * (1 + 2 + 3 + 4 + 5)  # every geometry was checked
+
+
+def test_band_plan_under_host_sanitizers(tmp_path):
+    """rt_render's cut of a frame into shards per device and row bands (rt_bands.h), built with
+    AddressSanitizer + UBSan: for heights 1..200, row blocks {1, 2, 3, 5, 16, 17, 48}, 1..64 shards over
+    1..min(shards, 8) devices, rows of 3, 24, 3 * 2^20 and 24 * 2^20 bytes and bands of 1 and 24 MiB, a
+    band is a positive multiple of lcm(row block, 16), the bands cover the slab with none empty,
+    per_dev * nb <= MAX_BANDS (the contexts' event arrays), the devices' shards partition the shards,
+    and all values equal the arithmetic rt_render had inline (tests/csrc/band_check.cpp)."""
+    import shutil
+    import subprocess
+
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "band_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(root, "tests", "csrc", "band_check.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    devices = sum(min(ns, 8) for ns in range(1, 65))
+    assert int(r.stdout) == 200 * 7 * devices * 4 * 2  # every geometry was checked
