@@ -205,9 +205,9 @@ def check(code: int, what: str = "") -> int:
 
 def launched(p, reset: bool = False) -> frozenset:
     """The kernel instantiations launched on context ``p`` since the last reset, each spelled as the
-    demangled name of its host stub (``k_walk<1, true, 2, true, true, false>``): the record that
+    demangled name of its host stub (``k_walk<1, true, 2, 1, true>``): the record that
     tests/dispatch_matrix.py's table is checked against."""
-    buf = ctypes.create_string_buffer(1 << 15)  # (195 names of at most 60 characters)
+    buf = ctypes.create_string_buffer(1 << 15)  # (183 names of at most 60 characters)
     need = check(lib().rt_debug_launched(p, buf, len(buf), int(reset)), "rt_debug_launched")
     if need > len(buf):
         raise RuntimeError(f"rt_debug_launched needs {need} bytes")

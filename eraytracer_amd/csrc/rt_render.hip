@@ -72,7 +72,10 @@ constexpr int TILE = 16;
 #include "rt_shade.inc"    // nearest-object scans, shadow tests, shading
 #include "rt_fused.inc"    // the fused engine (k_render)
 #include "rt_primary.inc"  // primary rays, the jitter, hit normals (shared with rt_attrs.hip)
-#include "rt_wave.inc"     // the wavefront engine (default)
+#include "rt_wave.inc"     // the wavefront engine (default): records, pass geometry, lists, pixel output
+#include "rt_wave_primary.inc" // ... its primary pass (k_pmask, k_primary)
+#include "rt_wave_walk.inc"    // ... its chain walks (walk_up, walk_fold, k_walk_deep, k_walk)
+#include "rt_wave_levels.inc"  // ... its per-level kernels (k_reflect, k_light, k_reflect_shade)
 #include "rt_selftest.inc" // the arithmetic self-test kernels
 
 } // namespace
@@ -98,7 +101,7 @@ struct LaunchRecord {
         {"k_reflect", 2, {-2, -2}},                     // LEVELS, ILP
         {"k_reflect_shade", 6, {2, -2, 3, -2, -2, -2}}, // PREC, GENPOW, SPH, ILP, BVH, LAST
         {"k_light", 3, {2, -2, 3}},                     // PREC, GENPOW, SPH
-        {"k_walk", 6, {2, -2, 3, -2, -2, -2}},          // PREC, GENPOW, SPH, BITS, DEEP, PAD
+        {"k_walk", 5, {2, -2, 3, 3, -2}},               // PREC, GENPOW, SPH, SRC, DEEP
         {"k_walk_deep", 2, {-2, 3}},                    // GENPOW, SPH
         {"k_accum", 1, {2}},                            // PREC
     }; // (tests/test_dispatch_matrix.py reads this table and compares it with the compiled stubs)
@@ -371,7 +374,7 @@ int rt_debug_stats(unsigned long long *out, int n, int reset) {
 
 // Test-only (not part of include/rt_mi355x.h; tests/dispatch_matrix.py): the kernel instantiations
 // launched on p since the last reset, one per line as the demangled name of its host stub
-// ("k_walk<1, true, 2, true, true, false>"), NUL-terminated, in buf[0, cap).  Returns the bytes the
+// ("k_walk<1, true, 2, 1, true>"), NUL-terminated, in buf[0, cap).  Returns the bytes the
 // whole text needs, the NUL included (text cut to cap when larger); reset != 0 then clears the record.
 int rt_debug_launched(rt_prepared *p, char *buf, int cap, int reset) {
     if (!p || cap < 0 || (cap > 0 && !buf)) return RT_EBADARG;
@@ -952,24 +955,22 @@ int wave_walks(rt_prepared *p, const WavePlan &pl, const WavePass &ps, int D) {
     const size_t ls_ = ps.lslots();
     const bool bits = hdr.n_light <= 32; // the shadow answers fit the record
     // deep: the merged walk (no k_walk_deep; without side streams); after k_reflect_shade
-    // (fuse) the shadow answers are in the children's records (PAD)
+    // (fuse) the shadow answers are in the children's records (ANS_REC), otherwise in k_light's array
     auto walk = [&](hipStream_t s_, int lo, int hi, bool deep) {
+        const int src = !bits ? ANS_TEST : deep && pl.fuse ? ANS_REC : ANS_LIT;
         with_sph(staged, sph_only, [&](auto sph) {
-            with_bool(bits, [&](auto bits_c) {
-                auto launch = [&](auto deep_c, auto pad_c) {
-                    p->launched.note(LaunchRecord::WALK, {PREC, GENPOW, decltype(sph)::value, decltype(bits_c)::value,
-                                                          decltype(deep_c)::value, decltype(pad_c)::value});
-                    hipLaunchKernelGGL((k_walk<PREC, GENPOW, decltype(sph)::value, decltype(bits_c)::value,
-                                               decltype(deep_c)::value, decltype(pad_c)::value>),
-                                       dim3(ps.sblocksw), dim3(BLOCK), pl.lds, s_, hdr, p->d_tab, p->d_itab, D, ps.o, ps.q,
-                                       ls_, ps.lists, ps.nitems, ps.colbuf, ps.child, ps.lit, lo, hi, ps.g);
-                };
-                // (PAD is launched with DEEP and BITS only; its instantiations without BITS
-                // exist, as they always have, and are never run: tests/dispatch_matrix.py lists
-                // them, with every other instantiation and the test that runs it)
-                if (deep && pl.fuse && bits) launch(std::true_type{}, std::true_type{});
-                else if (deep) launch(std::true_type{}, std::false_type{});
-                else launch(std::false_type{}, std::false_type{});
+            with_int<ANS_TEST, ANS_REC>(src, [&](auto src_c) {
+                with_bool(deep, [&](auto deep_c) {
+                    // (the records hold answers in the merged launch only: no other ANS_REC kernel exists)
+                    if constexpr (decltype(src_c)::value != ANS_REC || decltype(deep_c)::value) {
+                        p->launched.note(LaunchRecord::WALK, {PREC, GENPOW, decltype(sph)::value, decltype(src_c)::value,
+                                                              decltype(deep_c)::value});
+                        hipLaunchKernelGGL((k_walk<PREC, GENPOW, decltype(sph)::value, decltype(src_c)::value,
+                                                   decltype(deep_c)::value>),
+                                           dim3(ps.sblocksw), dim3(BLOCK), pl.lds, s_, hdr, p->d_tab, p->d_itab, D, ps.o,
+                                           ps.q, ls_, ps.lists, ps.nitems, ps.colbuf, ps.child, ps.lit, lo, hi, ps.g);
+                    }
+                });
             });
         });
     };

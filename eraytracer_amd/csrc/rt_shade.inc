@@ -387,10 +387,31 @@ __device__ __forceinline__ bool lit_by(const Scene &S, int light, const Target &
 // queued, tstore on the lanes that have such a child): light i's {dd, sp} — everything of its term
 // that does not depend on the reflected colour — goes to entry tslot (the child's slot) of `terms`,
 // for the chain walk to fold the child's colour in without shading the record again (walk_fold,
-// rt_wave.inc).
+// rt_wave_walk.inc).
 constexpr int TERM_MAX_LIGHTS = 8; // more lights: no entries, the walk reshades (walk_up)
 // double2 per entry: 64-byte entries up to 4 lights, 128-byte ones up to TERM_MAX_LIGHTS
 __host__ __device__ constexpr int term_stride(int n_light) { return n_light <= 4 ? 4 : 8; }
+
+// The fold of one light into a colour, the one copy that shade, shade_bits and walk_fold share (frames
+// are bit-identical to the reference because all three do these operations on these operands in this
+// order).  light_term: the light's colour term from its {dd, sp} (diffuse_term/4's and specular_term/7's
+// scalars), the material colour mc, the light's diffuse colour Lc and its specular colour Sc.
+__device__ __forceinline__ D3 light_term(double dd, double sp, const D3 &mc, const D3 &Lc, const D3 &Sc) {
+    const D3 diff = {mc.x * dd, mc.y * dd, mc.z * dd};
+    const D3 spec = {Sc.x * sp, Sc.y * sp, Sc.z * sp};
+    const D3 con = {diff.x + spec.x, diff.y + spec.y, diff.z + spec.z};
+    return D3{Lc.x * con.x, Lc.y * con.y, Lc.z * con.z};
+}
+// fold_light: F = F + (c * refl + lc * lit), the reflection added once per light (:239-247).  OPQ (c a
+// live value, not the background's constant): c is made opaque, so c * refl is formed per light as
+// written instead of being hoisted out of the caller's loop into three more live doubles.
+template <bool OPQ>
+__device__ __forceinline__ void fold_light(D3 &F, D3 c, double refl, const D3 &lc, double lit) {
+    if (OPQ) asm volatile("" : "+v"(c.x), "+v"(c.y), "+v"(c.z));
+    F.x = F.x + (c.x * refl + lc.x * lit);
+    F.y = F.y + (c.y * refl + lc.y * lit);
+    F.z = F.z + (c.z * refl + lc.z * lit);
+}
 template <bool GENPOW, int SPH = 0, bool NB = false, bool OPQ = false>
 __device__ __forceinline__ D3 shade(const Scene &S, int id, const D3 &d, const D3 &hit, const D3 &N, const D3 &col,
                                     double refl, bool active, unsigned *bits = nullptr, double2 *terms = nullptr,
@@ -421,26 +442,18 @@ __device__ __forceinline__ D3 shade(const Scene &S, int id, const D3 &d, const D
         // diffuse_term/4 (:272-279)
         const D3 ln = normalize3(D3{Lp.x - hit.x, Lp.y - hit.y, Lp.z - hit.z}, SPH && SL.h.norm_ok);
         const double dd = max0(dot3(N, ln));
-        const D3 diff = {mc.x * dd, mc.y * dd, mc.z * dd};
         // specular_term/7 (:285-297)
         const D3 hn = normalize3(D3{ln.x + -d.x, ln.y + -d.y, ln.z + -d.z});
         const double sp = shin * pow_libm<GENPOW>(max0(dot3(hn, N)), spow, active);
         if (terms && active && tstore) terms[(size_t)tslot * term_stride(h.n_light) + i] = double2{dd, sp};
-        const D3 spec = {Sc.x * sp, Sc.y * sp, Sc.z * sp};
-        const D3 con = {diff.x + spec.x, diff.y + spec.y, diff.z + spec.z};
         // A lane whose light term Lc (x) con is exactly zero gets the same bits for lit = 0 and
         // lit = 1 (the factor only multiplies signed zeros by 0 or 1): skip its shadow test.
-        const D3 lc = {Lc.x * con.x, Lc.y * con.y, Lc.z * con.z};
+        const D3 lc = light_term(dd, sp, mc, Lc, Sc);
         const bool need = active && !(lc.x == 0.0 && lc.y == 0.0 && lc.z == 0.0);
         // shadow ray direction normalize(Hit - Light) == -normalize(Light - Hit), bit for bit
         const bool lb = lit_by<SPH, NB>(SL, i, T, D3{-ln.x, -ln.y, -ln.z}, need, hb, Lp);
         if (bits && lb && i < 32) *bits |= 1u << i;
-        const double lit = lb ? 1.0 : 0.0;
-        D3 c = col;
-        if (OPQ) asm volatile("" : "+v"(c.x), "+v"(c.y), "+v"(c.z));
-        F.x = F.x + (c.x * refl + lc.x * lit);
-        F.y = F.y + (c.y * refl + lc.y * lit);
-        F.z = F.z + (c.z * refl + lc.z * lit);
+        fold_light<OPQ>(F, col, refl, lc, lb ? 1.0 : 0.0);
     }
     return F;
 }

@@ -1,22 +1,24 @@
 """Where every kernel instantiation of csrc/rt_render.hip is tested.
 
-rt_render.hip compiles 195 kernel instantiations, and rt_launch_rows, wave_level_lists, wave_reflect
+rt_render.hip compiles 183 kernel instantiations, and rt_launch_rows, wave_level_lists, wave_reflect
 and wave_walks pick among them at run time.  This module says, for each one, exactly one of:
 
 * ``("case", name)``: matrix case ``name`` (CASES below) launches it, and tests/test_gpu_dispatch_matrix.py
   renders that case, reads the context's launch record (rt_debug_launched) and fails unless the record
   holds the instantiation; every frame of the case is compared with brute force, the other precision
   and the oracle;
-* ``("elsewhere", test)``: not a render kernel; the named test runs it against its own reference;
-* ``("unreachable", condition)``: compiled, but the quoted dispatch condition never selects it.
+* ``("elsewhere", test)``: not a render kernel; the named test runs it against its own reference.
+
+No instantiation is compiled that the dispatch code cannot select.
 
 tests/test_dispatch_matrix.py builds the list of instantiations itself (the host stubs of a host-only
 compile) and fails on a stub this module does not classify, on an entry without a stub and on an entry
 classified twice: a kernel added later fails it until someone says here where it is tested.
 
 Names are spelled as ``nm -C`` spells the host stubs and as rt_debug_launched spells the record:
-``k_walk<1, true, 2, true, true, false>``.  PREC is 0 (binary64 frames) or 1 (binary32), SPH 0 (any
-scene), 1 (spheres only) or 2 (spheres only, tables staged in LDS).
+``k_walk<1, true, 2, 1, true>``.  PREC is 0 (binary64 frames) or 1 (binary32), SPH 0 (any
+scene), 1 (spheres only) or 2 (spheres only, tables staged in LDS); k_walk's SRC says where an
+ancestor's shadow answers come from: 0 tested again, 1 k_light's array, 2 the child's record.
 
 The scenes.  Every case is rendered with integer specular powers (hostile.unit_powers: 0 and 1, where
 pow is exact in glibc and in the kernels, so the frame equals the oracle's bit for bit) and with general
@@ -27,7 +29,6 @@ that leave pow_libm through pow() with lanes that take the binary powering.
 """
 from __future__ import annotations
 
-import itertools
 from collections import namedtuple
 
 import numpy as np
@@ -65,7 +66,7 @@ def relit(scene, m):
 # name -> (builder of the base scene, spheres only).  What makes each one take its kernels:
 #   s64, s64l8  staged (SPH 2), per-light terms of 64 and 128 bytes (walk_fold)
 #   s64l9       staged, more lights than TERM_MAX_LIGHTS: no terms
-#   s20l33      staged with more than 32 lights (shadow answers do not fit the records: BITS = false)
+#   s20l33      staged with more than 32 lights (shadow answers do not fit the records: SRC 0)
 #   s64l10      the first light count at which S64's tables no longer fit LDS_STAGE_MAX: SPH 1, no BVH
 #   s64l40      SPH 1, more than 32 lights
 #   s256        SPH 1, the BVH from reflection level 2 (its natural level)
@@ -167,13 +168,13 @@ S256, MIXED, MIXEDL40, DEFAULT = ("s256", 64, 48), ("mixed", 128, 96), ("mixedl4
 def _side(sph, many, few, few_spp):
     """Side streams on: k_light shades levels 0 and 1 beside the reflection chain (k_reflect), k_walk
     finishes the chains ending at level 1 and then the rest, k_walk_deep the deep levels (depth >= 3);
-    with more than 32 lights the walks shade again (BITS = false); a supersampled frame sums its
+    with more than 32 lights the walks test the shadows again (SRC 0); a supersampled frame sums its
     samples with k_accum."""
     return Case(f"sph{sph}-side", "wave",
                 [Frame(*few, 5 if few[0] != "s256" else 8), Frame(*many, 3 if sph == 2 else 4),
                  Frame(*few_spp, 4, spp=3)],
-                [f"k_light<{{P}}, {{G}}, {sph}>", f"k_walk<{{P}}, {{G}}, {sph}, true, false, false>",
-                 f"k_walk<{{P}}, {{G}}, {sph}, false, false, false>", f"k_walk_deep<{{G}}, {sph}>"])
+                [f"k_light<{{P}}, {{G}}, {sph}>", f"k_walk<{{P}}, {{G}}, {sph}, 1, false>",
+                 f"k_walk<{{P}}, {{G}}, {sph}, 0, false>", f"k_walk_deep<{{G}}, {sph}>"])
 
 
 def _levels(sph, many, few):
@@ -181,15 +182,15 @@ def _levels(sph, many, few):
     return Case(f"sph{sph}-levels", "wave",
                 [Frame(*few, 5 if few[0] != "s256" else 8, side=0, levels=True),
                  Frame(*many, 3 if sph == 2 else 4, side=0, levels=True)],
-                [f"k_walk<{{P}}, {{G}}, {sph}, true, true, false>", f"k_walk<{{P}}, {{G}}, {sph}, false, true, false>"])
+                [f"k_walk<{{P}}, {{G}}, {sph}, 1, true>", f"k_walk<{{P}}, {{G}}, {sph}, 0, true>"])
 
 
 def _depth2(sph, *scenes_):
     """Side streams off, no levels, depth 2: k_reflect_shade<!ILP> and the walk that finds the shadow
-    answers in the children's records (PAD)."""
+    answers in the children's records (SRC 2)."""
     return Case(f"sph{sph}-depth2", "wave", [Frame(*s, 2, side=0) for s in scenes_],
                 [f"k_reflect_shade<{{P}}, {{G}}, {sph}, false, false, false>",
-                 f"k_walk<{{P}}, {{G}}, {sph}, true, true, true>"])
+                 f"k_walk<{{P}}, {{G}}, {sph}, 2, true>"])
 
 
 CASES = [
@@ -260,16 +261,11 @@ def claims(case, prec, powers):
     return out
 
 
-# ---- the other two classes ------------------------------------------------------------------------
+# ---- the other class --------------------------------------------------------------------------------
 ELSEWHERE = {
     **{f"k_eval_math<{op}>": "tests/test_gpu_math_exact.py (rt_eval_math, op %d)" % op for op in range(7)},
     "k_selftest_math": "tests/test_gpu_parity.py::test_selftest_math (rt_selftest_math)",
 }
-
-# wave_walks: `if (deep && pl.fuse && bits) launch(DEEP, PAD)` is the only launch with PAD
-_NO_PAD = "wave_walks launches PAD only under `deep && pl.fuse && bits`: never with BITS = false"
-UNREACHABLE = {f"k_walk<{p}, {g}, {s}, false, true, true>": _NO_PAD
-               for p, g, s in itertools.product(PRECS, ("false", "true"), (0, 1, 2))}
 
 
 def table():
@@ -281,8 +277,6 @@ def table():
                 t.setdefault(c, []).append(("case", inst))
     for k, why in ELSEWHERE.items():
         t.setdefault(k, []).append(("elsewhere", why))
-    for k, why in UNREACHABLE.items():
-        t.setdefault(k, []).append(("unreachable", why))
     return t
 
 
