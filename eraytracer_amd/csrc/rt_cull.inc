@@ -62,6 +62,7 @@ __device__ __forceinline__ int sph_id(const Scene &S, int k) {
     return S.itab[S.h.i_sph_id + k];
 }
 // Copy the staged tables into this workgroup's LDS (every thread of the block, before any use).
+// The six offsets, and room for exactly these byte counts, are written by stage_lds_place (rt_layout.h).
 template <int SPH>
 __device__ __forceinline__ void stage_tables(const Scene &S) {
     if (SPH != 2) return;

@@ -140,4 +140,23 @@ inline size_t bvh_lds_place(SceneHdr &h, size_t base, int block) {
     return base + (size_t)block * h.bvh_depth * sizeof(unsigned);
 }
 
+// The LDS staging layout (SceneHdr's l_* fields): six 16-byte aligned sections in the order
+// stage_tables (rt_cull.inc) copies them, the reader of exactly these offsets and sizes — object
+// rows, object meta rows, the lights' per-origin sphere rows, the occluder masks (`ncell` cells),
+// the sphere ids, the sphere bounds.  Returns their total bytes for `ncell` occluder cells.  Only
+// one-cell masks are staged: with ncell == 1 and a total within LDS_STAGE_MAX the offsets and
+// l_bytes are set, otherwise they are -1 and l_bytes is 0 (nothing staged).
+inline long stage_lds_place(SceneHdr &h, int ncell) {
+    const long pairs = (long)h.n_light * h.n_sph;
+    const long bytes[6] = {(long)h.n_obj * OBJ_W * 8, (long)h.n_obj * OBJ_META_W * 4, pairs * SPH_ORG_W * 8,
+                           pairs * ncell * h.n_chunk * 8, (long)h.n_sph * 4, (long)h.n_sph * SPH_B_W * 8};
+    int *const at[6] = {&h.l_obj, &h.l_meta, &h.l_org, &h.l_occ, &h.l_id, &h.l_sphb};
+    long off[7] = {0};
+    for (int s = 0; s < 6; ++s) off[s + 1] = (off[s] + bytes[s] + 15) / 16 * 16;
+    const bool staged = ncell == 1 && off[6] <= LDS_STAGE_MAX;
+    for (int s = 0; s < 6; ++s) *at[s] = staged ? (int)off[s] : -1;
+    h.l_bytes = staged ? (int)off[6] : 0;
+    return off[6];
+}
+
 } // namespace rtl

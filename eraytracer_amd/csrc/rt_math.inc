@@ -151,8 +151,8 @@ __device__ __forceinline__ void dd_mul(double &ah, double &al, double bh, double
     ah = p;
     al = e;
 }
-// GENPOW: the scene has a specular power outside {0, 1, ..., 1024} (decided on the host, see
-// pow_int_ok in rt_scene.cpp), so the general device pow is compiled in; otherwise its large
+// GENPOW: the scene has a specular power outside {0, 1, ..., 1024} (SceneHdr::int_pow = 0, decided on
+// the host by shading_tables in rt_scene.cpp), so the general device pow is compiled in; otherwise its large
 // register footprint is kept out of the kernel.
 // x^n, n >= 1, by binary powering (the operations depend on n alone).  BR (n wave-uniform): the
 // multiplications sit under a branch the empty asm keeps one (if-converted, each ran for every step

@@ -97,15 +97,14 @@ def test_work_model():
 def test_scene_compiler_under_host_sanitizers(tmp_path):
     """The library's host code that parses caller input (rt_scene.cpp: check, canon, compile)
     built with AddressSanitizer + UBSan (host only; GPU sanitizers are unavailable) and run on
-    the default, S64, S256, adversarial and hostile (tests/hostile.py, tests/hostile_flat.py) scenes plus a
-    truncated list
-    and a lone camera."""
+    tests/scene_corpus.py: the default, S64, S256, mixed, adversarial and hostile (tests/hostile.py,
+    tests/hostile_flat.py) scenes, S2000, S2048 and S5000 around the occluder masks' bound, and the edge
+    lists (a lone camera, no object, no light, overflowing coordinates, a point sphere on a light,
+    duplicates around a non-object), of which the two bad ones must be refused."""
     import shutil
     import subprocess
 
-    from eraytracer_amd import _native as N
-    from tests import hostile, hostile_flat
-    from tests.test_oracle import TRICKY
+    from tests import scene_corpus
     if shutil.which("g++") is None:
         pytest.skip("no g++")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -113,24 +112,22 @@ def test_scene_compiler_under_host_sanitizers(tmp_path):
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=all", os.path.join(root, "tests", "csrc", "scene_check.cpp"),
                     os.path.join(root, "eraytracer_amd", "csrc", "rt_scene.cpp"), "-o", exe], check=True)
-    scenes_ = [R.scene(), scenes.s64(), scenes.s256()] + [mk() for mk in TRICKY]
-    scenes_ += [hostile.build(name) for name in hostile.NAMES]
-    scenes_ += [hostile_flat.build(name) for name in hostile_flat.NAMES]
+    corpus = scene_corpus.corpus()
     files = []
-    for i, sc in enumerate(scenes_):
-        el = N.marshal(sc)
+    for i, sc in enumerate(corpus.values()):
         p = tmp_path / f"s{i}.bin"
-        p.write_bytes(bytes(el))
+        p.write_bytes(scene_corpus.records(sc))
         files.append(str(p))
-    lone = tmp_path / "lone.bin"
-    lone.write_bytes(bytes(N.marshal(R.scene()[:1])))
-    files.append(str(lone))
     r = subprocess.run([exe] + files, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     rows = [ln.split() for ln in r.stdout.splitlines()]
     assert len(rows) == len(files)
-    for row in rows[:len(scenes_)]:
-        assert row[0] == "0" and row[2] == "0", row  # valid scenes compile
+    for name, row in zip(corpus, rows):
+        if name in scene_corpus.BAD:
+            assert row[2] == str(scene_corpus.BAD[name]), (name, row)
+        else:
+            assert row[0] == "0" and row[2] == "0", (name, row)  # valid scenes compile
+    assert set(scene_corpus.BAD) <= set(corpus) and len(corpus) > len(scene_corpus.BAD)
 
 
 def test_shard_mapping_under_host_sanitizers(tmp_path):
