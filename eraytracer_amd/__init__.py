@@ -12,9 +12,11 @@ from .raytracer import (  # noqa: F401
     raytraced_pixel_list_simple, render, standalone, tracing_function, write_pixels_to_ppm,
 )
 from .raytracer import nearest_hits, pick, render_attributes, shadow_factors  # noqa: F401
+from .raytracer import render_view, trace_rays, view_rays  # noqa: F401
 
 __all__ = [
     "scene", "render", "raytraced_pixel_list_simple", "raytraced_pixel_list_concurrent",
     "raytraced_pixel_list_distributed", "raytraced_pixel_list_gpu", "tracing_function", "raytrace", "go",
     "standalone", "write_pixels_to_ppm", "render_attributes", "pick", "nearest_hits", "shadow_factors",
+    "trace_rays", "view_rays", "render_view",
 ]

@@ -36,7 +36,7 @@ RT_CFG_KERNEL_TIMING = 2
 RT_CFG_CULL = 3
 RT_KT_PRIMARY, RT_KT_LEVEL1, RT_KT_RENDER, RT_KT_PMASK = 1, 2, 4, 8
 RT_LEVELS_HIT = 1
-RT_QUERY_ONE_ORIGIN = 1  # rt_query_rays / rt_query_shadow: one origin (light) for all n rays
+RT_QUERY_ONE_ORIGIN = 1  # rt_query_rays / rt_query_shadow / rt_query_colours: one origin (light) for all n rays
 RT_MAX_QUERY_RAYS = 1 << 30
 RT_ENGINE_WAVE, RT_ENGINE_FUSED = 0, 1
 # enum rt_eval_op (rt_eval_math, diagnostic)
@@ -46,7 +46,8 @@ RT_ENGINE_WAVE, RT_ENGINE_FUSED = 0, 1
 # every symbol include/rt_mi355x.h declares (tests/test_boundary.py checks the export list)
 EXPORTS = (
     "rt_abi_version", "rt_strerror", "rt_device_count", "rt_scene_check", "rt_scene_canon",
-    "rt_render", "rt_prepare", "rt_shard_rows", "rt_launch", "rt_launch_spp", "rt_launch_window", "rt_launch_samples", "rt_resolve", "rt_launch_attrs", "rt_query_rays", "rt_query_shadow", "rt_unshard", "rt_configure", "rt_release",
+    "rt_render", "rt_prepare", "rt_shard_rows", "rt_launch", "rt_launch_spp", "rt_launch_window", "rt_launch_samples", "rt_resolve", "rt_launch_attrs", "rt_query_rays", "rt_query_shadow",
+    "rt_query_colours_work_bytes", "rt_query_colours", "rt_unshard", "rt_configure", "rt_release",
     "rt_update_scene",
     "rt_ppm_bound", "rt_ppm_format", "rt_render_ppm_file",
     "rt_quantize", "rt_render_rawppm_file",
@@ -165,6 +166,9 @@ def lib() -> ctypes.CDLL:
                                   ctypes.POINTER(RtAttrPlanes), vp]
     L.rt_query_rays.argtypes = [vp, vp, vp, ctypes.c_uint64, u32, ctypes.POINTER(RtAttrPlanes), vp]
     L.rt_query_shadow.argtypes = [vp, vp, vp, vp, ctypes.c_uint64, u32, vp, vp]
+    L.rt_query_colours_work_bytes.restype = ctypes.c_size_t
+    L.rt_query_colours_work_bytes.argtypes = [ctypes.c_uint64, u32]
+    L.rt_query_colours.argtypes = [vp, vp, vp, ctypes.c_uint64, u32, u32, i32, vp, vp, vp, ctypes.c_size_t, vp]
     L.rt_ppm_bound.restype = ctypes.c_size_t
     L.rt_ppm_bound.argtypes = [u32, u32, u32]
     L.rt_ppm_format.argtypes = [vp, i32, u32, u32, u32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), vp]

@@ -75,16 +75,11 @@ namespace {
 #include "rt_primary.inc" // hit normals
 #include "rt_planes.inc"  // the attribute planes: a hit's attributes, the stores
 
+#include "rt_query.inc"   // SCAN_*, bvh_domain (the BVH's domain, see the top of this file)
+
 constexpr int QUERY_BLOCK = 256; // four waves
 constexpr int QUERY_GRID = 8192; // blocks at most: a batch above 2^21 rays loops
 enum { MODE_RAYS = 0, MODE_SHADOW = 1 };
-enum { SCAN_BRUTE = 0, SCAN_BEAM = 1, SCAN_BVH = 2 };
-
-// The BVH's domain (see the top of this file); E = hdr.ext + 1.
-__device__ __forceinline__ bool bvh_domain(const D3 &o, const D3 &d, double E) {
-    const double lim = 4.0 * E, dd = d.x * d.x + d.y * d.y + d.z * d.z;
-    return fabs(o.x) <= lim && fabs(o.y) <= lim && fabs(o.z) <= lim && fabs(dd - 1.0) <= 0x1p-20;
-}
 
 // a, b: the rays' origins and directions (MODE_RAYS) or the light and hit points (MODE_SHADOW), n
 // triples of doubles each — `a` one triple with one_origin; elem (MODE_SHADOW): the element each

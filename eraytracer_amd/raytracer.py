@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import time
 
 import numpy as np
@@ -347,6 +348,112 @@ def shadow_factors(lights, hits, elems, scene=None, *, device: int = 0):
         N.check(L.rt_query_shadow(ctx, d_l.data_ptr(), d_h.data_ptr(), d_e.data_ptr(), n,
                                   N.RT_QUERY_ONE_ORIGIN if lt.ndim == 1 else 0, lit.data_ptr(), stream), "rt_query_shadow")
     return lit.cpu().numpy()
+
+
+def trace_rays(origins, directions, depth, scene=None, *, precision: str = "f64", levels: bool = False, device: int = 0):
+    """The colour each of ``n`` rays of the caller's choosing sees (``rt_query_colours``, RT_QUERY in
+    include/rt_mi355x.h): ``pixel_colour_from_ray(Ray, Scene, depth)`` in the reference's fold order.
+    ``directions`` is ``(n, 3)``, used as given (not normalised); ``origins`` is ``(n, 3)`` or ``(3,)``, one
+    origin for every ray.  Returns an ``(n, 3)`` array — float64 or, with ``precision="f32"``, the float32
+    roundings of the same values — and with ``levels=True`` also an ``(n,)`` uint8 array, the number of
+    objects each ray's reflection chain hit (0: a miss).  Bad arguments raise ValueError before the
+    library is loaded."""
+    d = _triples(directions, "directions")
+    n = d.shape[0]
+    o = _triples(origins, "origins", n, shared=True)
+    _depth_ok(depth)
+    if precision not in ("f64", "f32"):
+        raise ValueError(f"badarg: precision must be 'f64' or 'f32', got {precision!r}")
+    if not isinstance(levels, (bool, np.bool_)):
+        raise ValueError(f"badarg: levels must be a bool, got {levels!r}")
+    _device_ok(device)
+    if scene is None:
+        scene = default_scene()
+    elems = N.marshal(scene)
+    fnp = np.float64 if precision == "f64" else np.float32
+    if n == 0:  # nothing to launch (and an empty tensor has no address to hand over)
+        rgb = np.empty((0, 3), dtype=fnp)
+        return (rgb, np.empty((0,), dtype=np.uint8)) if levels else rgb
+    L = N.lib()
+    import torch
+    dev = torch.device("cuda", int(device))
+    need = L.rt_query_colours_work_bytes(n, int(depth))
+    if need == 0 and depth != 0:
+        raise ValueError(f"badarg: the work space of {n} rays at depth {depth} overflows size_t")
+    rgb = torch.empty((n, 3), dtype=torch.float64 if precision == "f64" else torch.float32, device=dev)
+    lv = torch.empty((n,), dtype=torch.uint8, device=dev) if levels else None
+    work = torch.empty((need,), dtype=torch.uint8, device=dev) if need else None  # (torch allocations are 16-byte aligned)
+    d_o, d_d = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
+    with _prepared(L, elems, dev) as (ctx, stream):
+        N.check(L.rt_query_colours(ctx, d_o.data_ptr(), d_d.data_ptr(), n, int(depth),
+                                   N.RT_QUERY_ONE_ORIGIN if o.ndim == 1 else 0,
+                                   N.RT_OUT_F64 if precision == "f64" else N.RT_OUT_F32, rgb.data_ptr(),
+                                   lv.data_ptr() if levels else None, work.data_ptr() if need else None, need, stream),
+                "rt_query_colours")
+    out = rgb.cpu().numpy()
+    return (out, lv.cpu().numpy()) if levels else out
+
+
+def _vec3(v, what):
+    try:
+        a = np.array(v, dtype=np.float64)
+    except Exception:
+        raise ValueError(f"badarg: {what} is not a vector of three numbers: {v!r}") from None
+    if a.shape != (3,) or not np.isfinite(a).all():
+        raise ValueError(f"badarg: {what} must be three finite numbers, got {v!r}")
+    return a
+
+
+def view_rays(width: int, height: int, eye, target, up=(0, 1, 0), fov=90):
+    """The rays of a look-at pinhole camera: ``(eye (3,), directions (height*width, 3))``, float64,
+    row-major, computed in numpy::
+
+        fwd   = normalize(target - eye)
+        right = normalize(cross(up, fwd))
+        down  = cross(fwd, right)
+        hw    = tan(fov / 2)            (fov in degrees, the horizontal angle)
+        hh    = hw * height / width
+        pixel (x, y) looks along  normalize(fwd + (x/W - 0.5) 2 hw right + (y/H - 0.5) 2 hh down)
+
+    With ``eye`` at the reference camera looking along +z and ``up = (0, 1, 0)``, ``right`` is +x and
+    ``down`` is +y: the image has the reference's orientation (``point_on_screen/3``,
+    raytracer.erl:486-503).  The direction is evaluated as the reference evaluates its own, on a screen
+    of width 1 at the focal distance ``F = 1 / (2 hw)`` (``focal_length/2``, :483-484): the vector above
+    times F, ``F fwd + (x/W - 0.5) right + ((y/H - 0.5) H/W) down``, with the angle as ``fov * (pi / 180) /
+    2`` and ``vector_normalize/1``'s multiplication by ``1 / mag`` — so that a frame aimed like the
+    reference camera is the rendered frame, not a neighbour of it one rounding away (a reflection chain
+    can turn one unit in the last place of a direction into another colour).  ValueError for
+    ``target == eye``, an ``up`` parallel to ``fwd`` and a ``fov`` outside (0, 180)."""
+    if not _sizes_ok(width, height):
+        raise ValueError("function_clause: Width > 0, Height > 0 required (raytracer.erl:88-89)")
+    e, t, u = _vec3(eye, "eye"), _vec3(target, "target"), _vec3(up, "up")
+    if isinstance(fov, bool) or not isinstance(fov, (int, float, np.integer, np.floating)) or not 0 < fov < 180:
+        raise ValueError(f"badarg: fov must be a number of degrees in (0, 180), got {fov!r}")
+    fwd = t - e
+    if not fwd.any():
+        raise ValueError("badarg: target == eye: the camera looks nowhere")
+    fwd = fwd * (1 / math.sqrt(fwd @ fwd))
+    right = np.cross(u, fwd)
+    if not math.sqrt(right @ right) > 1e-12 * math.sqrt(u @ u):
+        raise ValueError("badarg: up is parallel to the viewing direction (or zero)")
+    right = right * (1 / math.sqrt(right @ right))
+    down = np.cross(fwd, right)
+    focal = 1 / (2 * math.tan(float(fov) * (math.pi / 180) / 2))
+    sx = np.arange(width) / width - 0.5
+    sy = (np.arange(height) / height - 0.5) * (height / width)
+    v = (focal * fwd)[None, None, :] + sx[None, :, None] * right[None, None, :] + sy[:, None, None] * down[None, None, :]
+    m2 = v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1] + v[..., 2] * v[..., 2]
+    d = v * (1 / np.sqrt(m2))[..., None]
+    return e, np.ascontiguousarray(d.reshape(height * width, 3))
+
+
+def render_view(width: int, height: int, depth: int, scene=None, *, eye, target, up=(0, 1, 0), fov=90,
+                precision: str = "f64", device: int = 0):
+    """A frame from a camera that is aimed: the ``(height, width, 3)`` colours of exactly the rays
+    :func:`view_rays` returns, traced by :func:`trace_rays` — nothing else.  The scene's own #camera{}
+    is not used (the reference camera's path, :func:`render`, is untouched)."""
+    e, d = view_rays(width, height, eye, target, up, fov)
+    return trace_rays(e, d, depth, scene, precision=precision, device=device).reshape(height, width, 3)
 
 
 def _has_lights(scene) -> bool:

@@ -467,7 +467,40 @@ int rt_launch_attrs(rt_prepared *p, uint32_t width, uint32_t height,
  * Checked before any HIP call and before p is read: RT_EBADARG for a null p, d_origin, d_dir, d_light,
  *   d_hit, d_elem, d_lit or out, an unknown flag bit, an input pointer that is not 8-byte aligned
  *   (d_elem: 4-byte), an `out` that fails rt_launch_attrs' plane checks (struct_size, all planes null,
- *   precision, alignment); RT_ETOOBIG for n > RT_MAX_QUERY_RAYS. */
+ *   precision, alignment); RT_ETOOBIG for n > RT_MAX_QUERY_RAYS.
+ * rt_query_colours: the colour ray i sees, d_rgb[3i..3i+2] = pixel_colour_from_ray(Ray_i, Scene, depth)
+ *   (raytracer.erl:186-252), for the rays of rt_query_rays (d_origin, d_dir, RT_QUERY_ONE_ORIGIN; the
+ *   direction used as given).  Mirror probes, light-field samples, orthographic, fisheye, stereo and
+ *   depth-of-field cameras, a camera that is aimed: each is one batch.  Depth 0 is {0,0,0} without a
+ *   scan and a miss is the background {0,0,0}; otherwise lighting_function/6 with the reflection added
+ *   once per light, in the reference's fold order — RT_ORDER_EXACT, no other order is offered — and
+ *   shadow_factor/4 as the renderer has it (matched by `canon`).  `precision` is RT_OUT_F64 or
+ *   RT_OUT_F32 (d_rgb's element); RT_OUT_F32 stores (float) of the binary64 value, nothing is computed
+ *   in binary32.  Bit-exactness holds in the same sense as for rendered frames: for rays whose
+ *   arithmetic stays finite in the reference every byte is the reference's, apart from the known pow
+ *   rounding (none with specular powers 0 and 1).
+ *   d_levels is optional (null: not wanted): d_levels[i] is the number of objects ray i's reflection
+ *   chain hit, rt_launch's definition — 0 is a miss, the count saturates at 255, and it is at most 1 in
+ *   a scene without point lights.
+ *   Ray i's bytes do not depend on n, on i, on the other rays of the batch, on RT_QUERY_ONE_ORIGIN
+ *   against a repeated origin, or on the context's configuration (RT_CFG_CULL, side streams).
+ *   Entries >= n of d_rgb and d_levels are never written.  A ray with a component that is not finite,
+ *   or one whose arithmetic overflows, gets unspecified values in its own entries; it causes no fault
+ *   and has no effect on any other ray.  A zero direction is inside the contract and misses everything.
+ *   d_work is caller-owned device memory, 16-byte aligned, of at least
+ *   rt_query_colours_work_bytes(n, depth) bytes (76 per ray and level, n rounded up to a multiple of
+ *   64); its contents are unspecified before and after the call, and the call owns it until `stream`
+ *   reaches the end of the call.  The size function is host-only and makes no HIP call; it returns 0
+ *   for depth 0 or n = 0 (then d_work may be null), and also 0 where the size overflows size_t.  There
+ *   is no limit on depth other than the work space the caller can allocate.
+ *   The call is asynchronous on `stream`, neither synchronises nor allocates, and uses none of the
+ *   context's work space.  n = 0 launches nothing and returns RT_OK.
+ *   Checked before any HIP call and before p is read, RT_EBADARG before RT_ETOOBIG: RT_EBADARG for a
+ *   null p, d_origin, d_dir or d_rgb, an unknown flag bit, a bad precision, an input pointer that is
+ *   not 8-byte aligned, a d_rgb not aligned to its element, and — for n <= RT_MAX_QUERY_RAYS with a
+ *   required size that is not zero — a d_work that is null or not 16-byte aligned, or work_bytes below
+ *   the required size; RT_ETOOBIG for n > RT_MAX_QUERY_RAYS (the work space is not looked at) and for
+ *   a required size that overflows size_t. */
 #define RT_QUERY_ONE_ORIGIN 1   /* d_origin / d_light holds ONE point (3 doubles) shared by all n rays */
 #define RT_MAX_QUERY_RAYS (1u << 30)
 
@@ -477,6 +510,11 @@ int rt_query_rays(rt_prepared *p, const double *d_origin, const double *d_dir, u
 int rt_query_shadow(rt_prepared *p, const double *d_light, const double *d_hit,
                     const int32_t *d_elem, uint64_t n, uint32_t flags,
                     uint8_t *d_lit, void *stream);
+
+size_t rt_query_colours_work_bytes(uint64_t n, uint32_t depth);
+int rt_query_colours(rt_prepared *p, const double *d_origin, const double *d_dir, uint64_t n,
+                     uint32_t depth, uint32_t flags, int precision,
+                     void *d_rgb, uint8_t *d_levels, void *d_work, size_t work_bytes, void *stream);
 /* Reassemble nshards gathered slabs (d_slabs = [nshards][shard_rows][W*3]) into the
  * row-major image d_image ([H][W*3]), on `stream`.  precision: the slabs' element, any of
  * RT_OUT_F64, RT_OUT_F32, RT_OUT_U8, RT_OUT_U16 (rows of W*3 elements of 8, 4, 1 or 2 bytes); the
